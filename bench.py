@@ -21,6 +21,8 @@ A "step" = one pass of the hot path over one synthetic batch already resident in
 all-reduce of the summed loss; the line then carries `multi_gpu` (ranks the backend saw, per-rank ms, the same
 per-GPU shard timed without the collective, the whole global batch on one GPU, speed-up and efficiency).  Every line carries `check`: two
 samples of the timed batch against the fp64 oracle (outside the timed region; --no-verify skips it).
+--dump-outputs DIR writes what the headline's last timed step returned (costs, gradients or a fixed sample of them) as
+.npy files: the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Workloads (BASELINE.json configs; lattice U = L+1 as tests/test_time.cu:56):
   c2: N=16  T=150  L=40  A=28   fp32      c3: N=128 T=150 L=20 A=5000 fp32  (default, headline)
@@ -360,6 +362,36 @@ def native_communicator(world, rank, dev, timeout_s=120.0):
     return state["rccl"], state["comm"]
 
 
+DUMP_SAMPLE = 1 << 22     # --dump-outputs: gradient elements kept of a larger gradient (16 MB fp32 + 32 MB fp64 indices)
+
+
+def dump_outputs(path, costs, grads, reduced=None):
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST timed step, as DIR/<name>.npy, so that two
+    builds can be compared output for output (the inputs are seeded: the same arguments give the same batch).
+      costs.npy               (N,) float32     the per-sample costs
+      grads.npy               float32          the whole gradient tensor, when it has at most DUMP_SAMPLE elements; else
+      grads_sample.npy        (k,) float32     a fixed sample of it (seed 0, sorted flat indices, the same for every run) and
+      grads_sample_index.npy  (k,) float64     those flat indices (exact in float64)
+      grads_sq_sum.npy        (grads.shape[0],) float64   sum of squares over every axis but the first (covers every element)
+      loss_reduced.npy        float64          sharded runs: the all-reduced loss this rank received"""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "costs.npy"), costs.detach().float().cpu().numpy())
+    flat = grads.detach().reshape(-1)
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        np.save(os.path.join(path, "grads.npy"), flat.float().cpu().numpy().reshape(tuple(grads.shape)))
+    else:
+        idx = np.unique(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+        np.save(os.path.join(path, "grads_sample.npy"), flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy())
+        np.save(os.path.join(path, "grads_sample_index.npy"), idx.astype(np.float64))
+    g2 = grads.detach().reshape(grads.shape[0], -1)
+    rows = max(1, (1 << 26) // max(1, g2.shape[1]))                 # fp64 temporaries of at most 512 MB
+    sq = torch.cat([g2[i:i + rows].double().square().sum(dim=1) for i in range(0, g2.shape[0], rows)])
+    np.save(os.path.join(path, "grads_sq_sum.npy"), sq.cpu().numpy())
+    if reduced is not None:
+        np.save(os.path.join(path, "loss_reduced.npy"), reduced.detach().double().cpu().numpy())
+
+
 def verify_batch(w, acts, labels, act_lens, label_lens, grads, costs, acts_picked=None):
     """Parity evidence for THIS run, outside the timed region: the first and the last sample of the timed batch (the
     gradients and costs the last timed step left behind) against the fp64 oracle on the same -- storage-rounded --
@@ -621,12 +653,17 @@ def main():
     ap.add_argument("--no-traffic-pass", action="store_true",
                     help="do not run the two extra rocprofv3 --pmc passes that measure `roofline.traffic` for this run "
                          "(one GPU only; the figure of the newest committed profiles/r*_traffic.json is reported instead)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline's last timed step computed (costs, gradients: a fixed "
+                         "sample when larger than %d elements) to DIR/<name>.npy, float32 / float64, rank 0" % DUMP_SAMPLE)
     ap.add_argument("--no-verify", action="store_true",
                     help="skip the parity check of the timed batch (two samples against the fp64 oracle, outside the "
                          "timed region; its result is the JSON line's `check` object)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     plain_line = not (args.override or args.varlen or args.packed or args.graph or args.aux_stream or args.pinned_costs
                       or args.force_sharded or args.in_place)
     want_extra = args.gpus == 1 and not args.no_extra and (args.extra or (args.workload is None and plain_line))
@@ -694,7 +731,7 @@ def main():
         dist.all_gather(every, mine)
         return [int(t[0]) for t in every]
 
-    def run_workload(name, steps, warmup, with_cpu):
+    def run_workload(name, steps, warmup, with_cpu, dump_dir=None):
         w = dict(WORKLOADS[name])
         for kv in filter(None, args.override.split(",")):
             k, v = kv.split("=")
@@ -732,7 +769,7 @@ def main():
                       assert lib.compute_rnnt_loss_async(*fargv) == 0
                       torch.cuda.synchronize(dev)
                   f0 = time.perf_counter()
-                  nfull = max(3, min(steps, 10))
+                  nfull = steps
                   for _ in range(nfull):
                       assert lib.compute_rnnt_loss_async(*fargv) == 0
                       torch.cuda.synchronize(dev)
@@ -903,6 +940,8 @@ def main():
         elapsed = time.perf_counter() - t0
         lib.rnnt_profile_enable(0)
         per_step = np.diff(np.array([t0] + marks)) * 1e3
+        if dump_dir is not None and rank == 0:
+            dump_outputs(dump_dir, costs, grads, out if sharded else None)
         # Small problems only: the same loop once more WITHOUT the per-stage HIP events (five event records per step
         # sit between the kernels; on a 0.08 ms step they are ~10 % of it, on c3 they are not measurable).  Reported
         # next to `value`, which stays the contractual events-on measurement.
@@ -991,7 +1030,8 @@ def main():
         torch.cuda.empty_cache()
         return res
 
-    r = run_workload(args.workload, args.steps, args.warmup, with_cpu=(not sharded and not args.no_cpu_baseline))
+    r = run_workload(args.workload, args.steps, args.warmup, with_cpu=(not sharded and not args.no_cpu_baseline),
+                     dump_dir=args.dump_outputs)
     w, ab = r["w"], r["bytes"]
     ms = r["ms_per_step"]
     U = w["L"] + 1
@@ -1071,7 +1111,7 @@ def main():
         # nobody should have to take the other numbers on the builder's word.  Protocol as the headline's (warmed, per-step
         # device sync, HIP-event stage times; the reference's own harness: tests/test_time.cu:89-128).
         extra = {}
-        esteps, ewarm = max(5, min(args.steps, 20)), max(2, min(args.warmup, 5))
+        esteps, ewarm = args.steps, max(2, min(args.warmup, 5))
         for key, name in OTHER_WORKLOADS.items():
             t_e = time.perf_counter()
             try:
@@ -1120,7 +1160,7 @@ def main():
         for key in MODULE_WORKLOADS:
             t_e = time.perf_counter()
             try:
-                rec = run_rnntloss_workload(dev, key, 50 if key.endswith("c2") else esteps, ewarm, verify=not args.no_verify)
+                rec = run_rnntloss_workload(dev, key, esteps, ewarm, verify=not args.no_verify)
             except Exception as exc:                                   # noqa: BLE001
                 extra[key] = {"error": repr(exc)[:400], "check": {"passed": False}}
                 torch.cuda.empty_cache()

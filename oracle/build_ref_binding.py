@@ -63,7 +63,9 @@ def build(kind):
     try:
         src = SRC
         cflags = ["-O1", "-I" + os.path.join(ROOT, "include")]
-        ldflags = ["-L" + LIBDIR, "-lwarprnnt", "-Wl,-rpath," + LIBDIR]
+        # $ORIGIN first, so that oracle/_ref/ works wherever the tree is copied to ("\\$$": ninja, then the shell);
+        # the absolute directory after it for the CPU test, which loads the module through a symlink
+        ldflags = ["-L" + LIBDIR, "-lwarprnnt", "-Wl,-rpath,\\$$ORIGIN/../../../warp-transducer_amd/lib", "-Wl,-rpath," + LIBDIR]
         if kind == "gpu":
             src = os.path.join(tmp, "binding_hip.cpp")
             with open(src, "w") as f:

@@ -15,6 +15,7 @@ LIB=$ROOT/warp-transducer_amd/lib
 [ -f "$REF/tests/test_gpu.cu" ] || { echo "reference checkout absent: keeping prebuilt oracle/_ref/ref_test_* (if any)"; exit 0; }
 [ -f "$LIB/libwarprnnt.so" ] || { echo "libwarprnnt.so not built yet"; exit 0; }
 OUT=$HERE/_ref
+# the library is found relative to the binary ($ORIGIN rpath), so oracle/_ref/ works wherever the tree is copied to
 mkdir -p "$OUT"
 TMP=$(mktemp -d)
 trap 'rm -rf "$TMP"' EXIT
@@ -30,6 +31,7 @@ for t in test_gpu test_time; do
   fi
   hipcc --offload-arch=gfx950 -O1 -std=c++14 -w -x hip -include hip/hip_runtime.h "${MAP[@]}" \
         -I"$ROOT/include" -I"$REF/tests" -c "$REF/tests/$t.cu" -o "$TMP/$t.o"
-  hipcc --offload-arch=gfx950 "$TMP/$t.o" "$TMP/random.o" -o "$OUT/ref_$t" -L"$LIB" -lwarprnnt -Wl,-rpath,"$LIB"
+  hipcc --offload-arch=gfx950 "$TMP/$t.o" "$TMP/random.o" -o "$OUT/ref_$t" -L"$LIB" -lwarprnnt \
+        -Wl,-rpath,'$ORIGIN/../../warp-transducer_amd/lib'
   echo "built $OUT/ref_$t from $REF/tests/$t.cu"
 done

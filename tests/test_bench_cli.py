@@ -59,3 +59,56 @@ def test_default_line_carries_every_workload_with_a_passing_check():
         assert ("roofline" in e) or ("mfma_roofline" in e) or key.startswith("rnntloss_"), key
     assert rec["other_workloads_all_checks_passed"]
     assert other["c5_full_1024_on_one_gpu"]["ms_per_step"] > 4 * other["c5_per_gpu"]["ms_per_step"]
+
+
+def _dumped(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+def test_dump_outputs_files_and_sample(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy files only, under 64 MB, with the gradient sample at the same indices
+    on every call: small gradients whole, large ones as a seeded sample with its flat indices."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    costs = torch.rand(3, generator=g)
+    small = torch.rand((3, 4, 5, 6), generator=g)
+    bench.dump_outputs(str(tmp_path / "s"), costs, small)
+    s = _dumped(tmp_path / "s")
+    assert set(s) == {"costs", "grads", "grads_sq_sum"}
+    assert np.array_equal(s["costs"], costs.numpy()) and np.array_equal(s["grads"], small.numpy())
+    assert np.allclose(s["grads_sq_sum"], (small.double() ** 2).sum(dim=(1, 2, 3)).numpy())
+    big = torch.rand((2, bench.DUMP_SAMPLE), generator=g).to(torch.bfloat16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), costs, big, reduced=torch.tensor([1.5, 3.0], dtype=torch.float64))
+    a, b = _dumped(tmp_path / "a"), _dumped(tmp_path / "b")
+    assert set(a) == {"costs", "grads_sample", "grads_sample_index", "grads_sq_sum", "loss_reduced"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(os.path.getsize(os.path.join(tmp_path, "a", f)) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    idx = a["grads_sample_index"].astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and idx[-1] < big.numel() and len(idx) > bench.DUMP_SAMPLE // 2
+    assert np.array_equal(a["grads_sample"], big.float().reshape(-1).numpy()[idx])
+
+
+@pytest.mark.gpu
+def test_dump_outputs_repeat_and_steps(tmp_path):
+    """Two runs with the same arguments dump the same outputs (seeded inputs); the line reports the --steps asked for, and
+    its per-step record holds exactly that many timed steps."""
+    import json
+    import numpy as np
+    recs = []
+    for d, steps in (("a", "3"), ("b", "4")):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c2", "--steps", steps,
+                              "--warmup", "1", "--no-cpu-baseline", "--no-traffic-pass", "--dump-outputs", str(tmp_path / d)],
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        recs.append(json.loads(out.stdout.strip().splitlines()[-1]))
+    assert [r["steps"] for r in recs] == [3, 4] and [r["step_ms"]["n"] for r in recs] == [3, 4]
+    a, b = _dumped(tmp_path / "a"), _dumped(tmp_path / "b")
+    assert set(a) == set(b) and {"costs", "grads_sq_sum"} <= set(a)
+    assert a["costs"].shape == (16,) and np.isfinite(a["costs"]).all()
+    for k in a:
+        assert np.allclose(a[k], b[k], rtol=1e-6, atol=1e-7), k

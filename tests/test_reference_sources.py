@@ -134,9 +134,17 @@ def _ref_binary(name):
     return path
 
 
+def _run_ref(argv):
+    """Runs a prebuilt oracle/_ref program against THIS checkout's libwarprnnt.so.  oracle/_ref/ is built where the
+    reference sources are and carried to the GPU box as it is, so the run names the library under test itself instead of
+    relying on the search path recorded in the binary (LD_LIBRARY_PATH is searched before a RUNPATH)."""
+    env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(filter(None, [LIBDIR, os.environ.get("LD_LIBRARY_PATH")])))
+    return subprocess.run(argv, capture_output=True, text=True, timeout=900, env=env)
+
+
 @pytest.mark.gpu
 def test_reference_test_gpu_cu():
-    out = subprocess.run([_ref_binary("ref_test_gpu")], capture_output=True, text=True, timeout=900)
+    out = _run_ref([_ref_binary("ref_test_gpu")])
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "Tests pass" in out.stdout, out.stdout[-2000:]
     for name in ("small_test 1", "options_test 1", "inf_test 1"):
@@ -146,6 +154,6 @@ def test_reference_test_gpu_cu():
 @pytest.mark.gpu
 def test_reference_test_time_cu():
     """tests/test_time.cu: `test_time B T L A` (README row T=150, L=40, A=28, N=16): ten timed calls, it prints their mean."""
-    out = subprocess.run([_ref_binary("ref_test_time"), "16", "150", "40", "28"], capture_output=True, text=True, timeout=900)
+    out = _run_ref([_ref_binary("ref_test_time"), "16", "150", "40", "28"])
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "average 10 time cost" in out.stdout, out.stdout[-2000:]
