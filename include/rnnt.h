@@ -317,8 +317,10 @@ rnntStatus_t compute_rnnt_loss_likelihoods(const void* workspace,
  * whose table exceeds 32 MB, the FIRST samples of the batch have lost their alpha / beta: for those the two arrays come back
  * all NaN.  Every sample is intact after a score-only call (gradients == NULL / prepare_backward == 0: same alpha, and a
  * score-only call runs no beta sweep: beta is undefined then) -- and in any call whose record table is at most 32 MB
- * (T * U * minibatch <= 2 M cells for an fp32 lattice): debugging shapes.  The likelihoods of
- * compute_rnnt_loss_likelihoods are kept for every sample in every case. */
+ * (T * U * minibatch <= 2 M cells for an fp32 lattice): debugging shapes.  One exception: a PACKED call with a grad_scale
+ * (compute_rnnt_loss_packed*, the packed two-phase pair) keeps one scale per packed row in the lattice blocks of the first
+ * samples, whatever the table's size; those samples come back all NaN too.  A sample's dump is either its exact alpha / beta
+ * or all NaN.  The likelihoods of compute_rnnt_loss_likelihoods are kept for every sample in every case. */
 rnntStatus_t compute_rnnt_loss_lattice_dump(const void* workspace,
                                             const int* const label_lengths,
                                             const int* const input_lengths,

@@ -146,3 +146,105 @@ def test_record_table_overlays_consumed_lattice_blocks(oracle, shape, packed):
         Tb, Ub = int(tl[0]), int(ll[0]) + 1
         lp = torch.log_softmax(x[0, Tb - 1, Ub - 1].double().cpu(), -1).numpy()
         assert np.isfinite(a0[:Tb, :Ub]).all() and abs(-(a0[Tb - 1, Ub - 1] + lp[0]) - ref_c[0]) <= 1e-4 * abs(ref_c[0])
+
+
+def diagonal_lattice(lp, labels, T, U, blank):
+    """numpy_lattice's recursions one anti-diagonal at a time (vectorised along it: long lattices in seconds)."""
+    lpb = lp[:, :, blank]
+    lpl = np.full((T, U), -np.inf)
+    if U > 1:
+        lpl[:, :U - 1] = np.take_along_axis(lp[:, :U - 1, :], np.asarray(labels[:U - 1], dtype=np.int64)[None, :, None], 2)[:, :, 0]
+    a = np.full((T, U), -np.inf); b = np.full((T, U), -np.inf)
+    a[0, 0] = 0.0
+    for n in range(1, T + U - 1):
+        t = np.arange(max(0, n - U + 1), min(T - 1, n) + 1); u = n - t
+        up = np.where(t > 0, a[np.maximum(t - 1, 0), u] + lpb[np.maximum(t - 1, 0), u], -np.inf)
+        left = np.where(u > 0, a[t, np.maximum(u - 1, 0)] + lpl[t, np.maximum(u - 1, 0)], -np.inf)
+        a[t, u] = np.logaddexp(up, left)
+    b[T - 1, U - 1] = lpb[T - 1, U - 1]
+    for n in range(T + U - 3, -1, -1):
+        t = np.arange(max(0, n - U + 1), min(T - 1, n) + 1); u = n - t
+        down = np.where(t < T - 1, b[np.minimum(t + 1, T - 1), u] + lpb[t, u], -np.inf)
+        right = np.where(u < U - 1, b[t, np.minimum(u + 1, U - 1)] + lpl[t, u], -np.inf)
+        b[t, u] = np.logaddexp(down, right)
+    return a, b
+
+
+def test_diagonal_lattice_equals_the_plain_one():
+    rng = np.random.default_rng(5)
+    for T, U, A in ((1, 1, 3), (1, 4, 3), (5, 1, 2), (7, 5, 4)):
+        lp = torch.log_softmax(torch.tensor(rng.standard_normal((T, U, A))), -1).numpy()
+        labels = rng.integers(1, A, size=U - 1)
+        for x, y in zip(numpy_lattice(lp, labels, T, U, 0), diagonal_lattice(lp, labels, T, U, 0)):
+            assert np.allclose(x, y, rtol=0, atol=1e-12, equal_nan=True)
+
+
+# the dump contract after every entry form: (layout, scaled, second stream, shape); the first two shapes keep the record
+# table below 32 MB, (16, 800, 200, 2) takes it above.  (6, 761, 9, 3) has 769 diagonals: the two-half schedule runs with a
+# second stream.  (8, 64, 64, 5), every sample full: the packed row scales fall on sample 0's alpha.
+_SMALL_PADDED, _SMALL_PACKED, _LARGE = (6, 761, 9, 3), (8, 64, 64, 5), (16, 800, 200, 2)
+_DUMP_CASES = [(lay, scaled, aux, shape) for lay in ("padded", "packed") for scaled in (False, True) for aux in (False, True)
+               for shape in ((_SMALL_PADDED if lay == "padded" else _SMALL_PACKED), _LARGE) if not (lay == "packed" and aux)]
+
+
+@pytest.mark.parametrize("layout,scaled,aux,shape", _DUMP_CASES,
+                         ids=["%s-%s-%s-%s" % (c[0], "scaled" if c[1] else "unscaled", "two_half" if c[2] else "one_stream",
+                                               "large" if c[3] == _LARGE else "small") for c in _DUMP_CASES])
+def test_dump_is_exact_or_nan_after_every_entry_form(layout, scaled, aux, shape):
+    """After a gradient-computing call, EVERY sample's dump is its alpha / beta (within the tolerance above) or all NaN: a finite
+    value that differs is the failure (rnnt.h, compute_rnnt_loss_lattice_dump)."""
+    from warprnnt_pytorch import _lib, warp_rnnt
+    from warprnnt_pytorch.packed import pack_joint, row_offsets
+    lib = _lib.lib()
+    N, T, U, A = shape
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(sum(shape) + 2 * scaled + aux)
+    x = torch.tensor(rng.standard_normal(shape).astype(np.float32), device=dev)
+    labels = rng.integers(1, A, size=(N, U - 1)).astype(np.int32)
+    if shape == _SMALL_PACKED:
+        tl = np.full(N, T, np.int32); ll = np.full(N, U - 1, np.int32)
+    else:
+        tl = rng.integers(T // 2, T + 1, size=N).astype(np.int32); tl[0] = T; tl[N - 1] = T
+        ll = rng.integers((U - 1) // 2, U, size=N).astype(np.int32); ll[0] = U - 1; ll[N - 1] = U - 1
+    t_lab, t_tl, t_ll = (torch.tensor(v, device=dev) for v in (labels, tl, ll))
+    ws = torch.empty(_lib.workspace_bytes(T, U, N, True, 4), dtype=torch.uint8, device=dev)
+    ws.fill_(0xA5)
+    opt = _lib.rnntOptions(loc=1, num_threads=0, stream=torch.cuda.current_stream(dev).cuda_stream, blank_label=0, maxT=T, maxU=U,
+                           batch_first=True)
+    scale = torch.tensor(0.5 + 0.25 * np.arange(N), dtype=torch.float32, device=dev) if scaled else None
+    costs = torch.zeros(N, device=dev)
+    if layout == "packed":
+        p = pack_joint(x, t_tl, t_ll).contiguous()
+        offs = row_offsets(t_tl, t_ll)
+        g = torch.empty_like(p)
+        st = lib.compute_rnnt_loss_packed(p.data_ptr(), g.data_ptr(), t_lab.data_ptr(), t_ll.data_ptr(), t_tl.data_ptr(), offs.data_ptr(),
+                                          p.shape[0], A, N, costs.data_ptr(), scale.data_ptr() if scaled else None, ws.data_ptr(), opt,
+                                          _lib.DT_F32, 0.0)
+        assert st == 0
+    else:
+        if aux:
+            warp_rnnt.set_aux_stream(torch.cuda.Stream(dev))
+        try:
+            warp_rnnt.gpu_rnnt_async(x, t_lab, t_tl, t_ll, costs, torch.empty_like(x), 0, grad_scale=scale, workspace=ws)
+        finally:
+            if aux:
+                warp_rnnt.set_aux_stream(None)
+    torch.cuda.synchronize()
+    a_out = torch.zeros(T * U, dtype=torch.float64, device=dev); b_out = torch.zeros_like(a_out)
+    intact = []
+    for b in range(N):
+        assert lib.compute_rnnt_loss_lattice_dump(ws.data_ptr(), t_ll.data_ptr(), t_tl.data_ptr(), N, b, opt, _lib.DT_F32, a_out.data_ptr(),
+                                                  b_out.data_ptr()) == 0
+        torch.cuda.synchronize()
+        ga, gb = a_out.view(T, U).cpu().numpy(), b_out.view(T, U).cpu().numpy()
+        if np.isnan(ga).all() and np.isnan(gb).all():
+            continue                                                    # overlaid: announced as such
+        Tb, Ub = int(tl[b]), int(ll[b]) + 1
+        lp = torch.log_softmax(x[b, :Tb, :Ub].double().cpu(), -1).numpy()
+        ra, rb = diagonal_lattice(lp, labels[b], Tb, Ub, 0)
+        tol = 2e-4 * max(1.0, np.abs(ra).max() / 30)
+        da, db = np.abs(ga[:Tb, :Ub] - ra).max(), np.abs(gb[:Tb, :Ub] - rb).max()
+        assert da <= tol and db <= tol, ("sample %d: finite but wrong" % b, da, db, tol)
+        assert np.isnan(ga[Tb:]).all() and np.isnan(ga[:, Ub:]).all() and np.isnan(gb[Tb:]).all() and np.isnan(gb[:, Ub:]).all()
+        intact.append(b)
+    assert N - 1 in intact, intact                                      # the last sample is never overlaid

@@ -177,8 +177,14 @@ static void launch_grad(Plan<typename Tag::comp>& p, const typename Tag::store* 
         CC* rowscale = nullptr;
         if (packed && grad_scale) {
             rowscale = p.rowscale;                 // (lattice blocks that are dead by now: make_layout)
+            // the blocks, counted from sample 0, that the row scales overlay (rowscale starts at or behind the head: the first
+            // block is sample 0's even when the record table overlays nothing) -- for compute_rnnt_loss_lattice_dump
+            const size_t end = static_cast<size_t>(reinterpret_cast<const char*>(rowscale) - reinterpret_cast<const char*>(p.rowtab)) +
+                               static_cast<size_t>(p.packed_rows) * sizeof(CC);
+            const int recycled = end <= p.head_bytes || p.block_bytes == 0 ? 0
+                               : static_cast<int>((end - p.head_bytes + p.block_bytes - 1) / p.block_bytes);
             hipLaunchKernelGGL((fill_row_scale_kernel<CC>), dim3(p.N, 8), dim3(256), 0, p.stream, p.offsets, grad_scale,
-                               rowscale, static_cast<long long>(p.packed_rows));
+                               rowscale, static_cast<long long>(p.packed_rows), p.padflag, recycled);
         }
 #define RNNT_FLAT(SC, PP, PS)                                                                                       \
     hipLaunchKernelGGL((grad_flat_kernel<Tag, SC, PP, PS>), dim3(grid), dim3(256), 0, p.stream, acts, grads,        \

@@ -87,7 +87,9 @@ static Layout make_layout(int maxT, int maxU, int N, size_t lat, bool joint) {
     l.beta = head + lat_block_beta(maxT, maxU, static_cast<int>(Up)) * lat;
     size_t o = align_up(head + block * N);
     // one scale per packed row (packed layout with grad_scale): behind the record table's last possible row, inside blocks
-    // that are dead when the gradient stage starts (5 lat T U N <= head + N block)
+    // that are dead when the gradient stage starts (5 lat T U N <= head + N block).  Below kOneGroupBytes the head is the whole
+    // table and rowscale == head: the scales overlay the blocks of the FIRST samples (sample 0's from its first byte) even
+    // though the records overlay none -- launch_grad counts those blocks into padflag[2] (the lattice dump's NaN samples)
     l.rowscale = align_up(recs);
     if (l.rowscale + static_cast<size_t>(maxT) * maxU * N * lat > o) o = align_up(l.rowscale + static_cast<size_t>(maxT) * maxU * N * lat);   // (cannot happen: kept as a guard)
     l.offa = o;  o = align_up(o + D * W * N * sizeof(double));

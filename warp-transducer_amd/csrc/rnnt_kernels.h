@@ -2051,12 +2051,14 @@ static __global__ __launch_bounds__(256) void loss_sum_kernel(const C* __restric
 // ------------------------------------------------------------------------------------------
 // Packed layout with a per-sample gradient scale: one scale per packed ROW, so that the gradient kernel's lookup
 // needs no search (rowscale lives in lattice blocks of the workspace that are dead once the coefficients exist: make_layout).
-// grid = (N, 8), block = 256.
+// Those blocks lose their alpha / beta: `recycled` (launch_grad) is raised into padflag[2] for the lattice dump, as the
+// coefficient kernels do for the record table.  grid = (N, 8), block = 256.
 template <typename C>
 static __global__ __launch_bounds__(256) void fill_row_scale_kernel(
         const long long* __restrict__ offsets, const C* __restrict__ grad_scale, C* __restrict__ rowscale,
-        long long total_rows) {
+        long long total_rows, int* __restrict__ padflag, int recycled) {
     const int b = blockIdx.x;
+    if (recycled > 0 && b == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicMax(padflag + 2, recycled);
     const long long lo = offsets[b], hi = offsets[b + 1] < total_rows ? offsets[b + 1] : total_rows;
     const C s = grad_scale[b];
     for (long long r = lo + static_cast<long long>(blockIdx.y) * 256 + threadIdx.x; r < hi;
