@@ -530,6 +530,50 @@ rnntStatus_t compute_rnnt_loss_add_bwd_dt(const void* trans_acts,
                                           rnntOptions options,
                                           int dtype_code);
 
+/* Best-path (Viterbi) alignment through the lattice the loss sums over (extension).  For sample b with T_b = input_lengths[b]
+ * frames and U_b = label_lengths[b] labels, a path runs from (0,0) to (T_b-1, U_b) by blank (t,u)->(t+1,u) and label
+ * (t,u)->(t,u+1) steps and ends with the final blank -- the loss's lattice, its label == blank and -inf conventions included.
+ *   score[b]      the natural-log probability of the best path (always <= -cost[b] of the loss); -inf when every path is
+ *                 forbidden by -inf log-probabilities, NaN when the sample's activations hold a NaN (neither is an error)
+ *   frames[b*(maxU-1) + u]  for u < U_b: the frame at which label u is emitted (non-decreasing, in [0, T_b-1]; they
+ *                 determine the path); -1 for u >= U_b, and everywhere when the score is not finite
+ * Ties: when the two predecessors of a cell are exactly equal the blank one (t-1,u) wins -- labels are emitted as early as
+ * possible (uniform logits: every frame 0).  score is a double array, frames an int32 array of minibatch x (maxU - 1)
+ * (may be NULL when maxU == 1).
+ * RNNT_GPU: activations are raw LOGITS as for compute_rnnt_loss_async, dtype_code the same (0 fp32, 1 fp64, 2 bf16, 3 fp16);
+ * every pointer is a DEVICE pointer; the call only enqueues on options.stream (no synchronisation); the workspace is the
+ * one get_workspace_size(maxT, maxU, minibatch, true, &bytes, element size) returns.
+ * RNNT_CPU: activations are LOG-PROBS (dtype_code 0 fp32 or 1 fp64), every pointer is a host pointer, the workspace is
+ * get_workspace_size(..., false, ...); lengths that do not fit the tensor return RNNT_STATUS_INVALID_VALUE.
+ * Invalid arguments: RNNT_STATUS_INVALID_VALUE, as the loss entries. */
+rnntStatus_t compute_rnnt_align(const void* activations,
+                                const int* const flat_labels,
+                                const int* const label_lengths,
+                                const int* const input_lengths,
+                                int alphabet_size,
+                                int minibatch,
+                                double* score,
+                                int* frames,
+                                void* workspace,
+                                rnntOptions options,
+                                int dtype_code);
+
+/* compute_rnnt_align for the additive joint h(k,t,u) = trans_acts[b,t,k] + pred_acts[b,u,k] (see compute_rnnt_loss_add):
+ * GPU only, dtype_code as compute_rnnt_loss_add_fwd_dt (0 fp32, 2 bf16, 3 fp16), workspace from get_workspace_size_add().
+ * Same outputs, same conventions, enqueue only. */
+rnntStatus_t compute_rnnt_align_add(const void* trans_acts,
+                                    const void* pred_acts,
+                                    const int* const flat_labels,
+                                    const int* const label_lengths,
+                                    const int* const input_lengths,
+                                    int alphabet_size,
+                                    int minibatch,
+                                    double* score,
+                                    int* frames,
+                                    void* workspace,
+                                    rnntOptions options,
+                                    int dtype_code);
+
 /* Two-half schedule for long lattices (extension).  The alpha/beta recursion is a dependent chain: on long utterances (T + U in the
  * thousands) it takes hundreds of microseconds during which a few small blocks hold the device and HBM idles, between the two
  * streaming stages.  Given a SECOND stream, the one-call gradient-computing entry points above (compute_rnnt_loss and its fp64 /

@@ -158,6 +158,65 @@ rnntStatus_t run(const R* log_probs, R* grads, const int* labels, const int* lab
     return bad ? RNNT_STATUS_INVALID_VALUE : RNNT_STATUS_SUCCESS;
 }
 
+// Viterbi over one sample's lattice in fp64: v[t*U + u] = best log-probability of a path prefix ending in (t, u).  The label
+// predecessor (t, u-1) wins only when it is STRICTLY better than the blank one (t-1, u): ties emit labels as early as possible.
+// The traceback recomputes the same comparison from v.  Returns the score; frames[u] for u < U-1.
+template <typename R>
+double align_sample(const R* lp, size_t t_stride, size_t u_stride, const int* y, int T, int U, int blank, double* v,
+                    int* frames) {
+    const double NEG = -std::numeric_limits<double>::infinity();
+    auto pb = [&](int t, int u) { return static_cast<double>(lp[t * t_stride + u * u_stride + blank]); };
+    auto pl = [&](int t, int u) { return static_cast<double>(lp[t * t_stride + u * u_stride + y[u]]); };
+    bool nan = false;
+    for (int t = 0; t < T; ++t)
+        for (int u = 0; u < U; ++u) {
+            nan = nan || std::isnan(pb(t, u)) || (u + 1 < U && std::isnan(pl(t, u)));
+            if (t == 0 && u == 0) { v[0] = 0.0; continue; }
+            const double stay = t > 0 ? v[(t - 1) * U + u] + pb(t - 1, u) : NEG;
+            const double emit = u > 0 ? v[t * U + u - 1] + pl(t, u - 1) : NEG;
+            v[t * U + u] = emit > stay ? emit : stay;
+        }
+    const double s = v[(T - 1) * U + U - 1] + pb(T - 1, U - 1);
+    if (nan) return std::numeric_limits<double>::quiet_NaN();
+    if (!(s > NEG)) return s;
+    int t = T - 1, u = U - 1;
+    while (t > 0 || u > 0) {
+        const bool label = u > 0 && (t == 0 || v[t * U + u - 1] + pl(t, u - 1) > v[(t - 1) * U + u] + pb(t - 1, u));
+        if (label) { frames[u - 1] = t; --u; } else { --t; }
+    }
+    return s;
+}
+
+template <typename R>
+rnntStatus_t run_align(const R* log_probs, const int* labels, const int* label_lengths, const int* input_lengths, int A,
+                       int N, double* score, int* frames, void* workspace, const rnntOptions& opt) {
+    const int maxT = opt.maxT, maxU = opt.maxU, blank = opt.blank_label;
+    if (blank < 0 || blank >= A) return RNNT_STATUS_INVALID_VALUE;
+    for (int b = 0; b < N; ++b) {
+        const int T = input_lengths[b], U = label_lengths[b] + 1;
+        if (T <= 0 || T > maxT || U <= 0 || U > maxU) return RNNT_STATUS_INVALID_VALUE;
+    }
+    // one double per cell and sample: inside cpu_workspace_bytes() (four lattice values per cell) for either lattice size
+    double* scratch = static_cast<double*>(workspace);
+    const size_t slab = static_cast<size_t>(maxT) * maxU * A;
+    const bool bf = opt.batch_first;
+    const int threads = opt.num_threads > 0 ? static_cast<int>(opt.num_threads) : omp_get_max_threads();
+#pragma omp parallel for schedule(dynamic) num_threads(threads) if (N > 1)
+    for (int b = 0; b < N; ++b) {
+        const int T = input_lengths[b], U = label_lengths[b] + 1;
+        const size_t u_stride = bf ? static_cast<size_t>(A) : static_cast<size_t>(N) * A;
+        const R* lp = log_probs + (bf ? b * slab : static_cast<size_t>(b) * A);
+        int* fr = frames + static_cast<size_t>(b) * (maxU - 1);
+        for (int u = 0; u < maxU - 1; ++u) fr[u] = -1;
+        const double s = align_sample<R>(lp, u_stride * maxU, u_stride, labels + static_cast<size_t>(b) * (maxU - 1), T, U,
+                                         blank, scratch + static_cast<size_t>(b) * maxT * maxU, fr);
+        if (!std::isfinite(s))
+            for (int u = 0; u < maxU - 1; ++u) fr[u] = -1;
+        score[b] = s;
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
 }  // namespace
 
 size_t cpu_workspace_bytes(int maxT, int maxU, int minibatch, size_t lat) {
@@ -184,6 +243,16 @@ rnntStatus_t cpu_rnnt_packed(const void* log_probs, void* grads, const int* labe
                            input_lengths, A, N, static_cast<double*>(costs), workspace, opt, offsets);
     return run<float>(static_cast<const float*>(log_probs), static_cast<float*>(grads), labels, label_lengths,
                       input_lengths, A, N, static_cast<float*>(costs), workspace, opt, offsets);
+}
+
+rnntStatus_t cpu_rnnt_align_f32(const float* log_probs, const int* labels, const int* label_lengths, const int* input_lengths,
+                                int A, int N, double* score, int* frames, void* workspace, const rnntOptions& opt) {
+    return run_align<float>(log_probs, labels, label_lengths, input_lengths, A, N, score, frames, workspace, opt);
+}
+
+rnntStatus_t cpu_rnnt_align_f64(const double* log_probs, const int* labels, const int* label_lengths, const int* input_lengths,
+                                int A, int N, double* score, int* frames, void* workspace, const rnntOptions& opt) {
+    return run_align<double>(log_probs, labels, label_lengths, input_lengths, A, N, score, frames, workspace, opt);
 }
 
 }  // namespace rnnt

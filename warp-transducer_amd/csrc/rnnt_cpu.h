@@ -17,4 +17,9 @@ rnntStatus_t cpu_rnnt_f64(const double* log_probs, double* grads, const int* lab
 rnntStatus_t cpu_rnnt_packed(const void* log_probs, void* grads, const int* labels, const int* label_lengths,
                              const int* input_lengths, const long long* offsets, int A, int N, void* costs,
                              void* workspace, const rnntOptions& opt, bool fp64);
+// best-path alignment (compute_rnnt_align with options.loc == RNNT_CPU): log-probs in, natural-log scores, frames (N, maxU-1)
+rnntStatus_t cpu_rnnt_align_f32(const float* log_probs, const int* labels, const int* label_lengths, const int* input_lengths,
+                                int A, int N, double* score, int* frames, void* workspace, const rnntOptions& opt);
+rnntStatus_t cpu_rnnt_align_f64(const double* log_probs, const int* labels, const int* label_lengths, const int* input_lengths,
+                                int A, int N, double* score, int* frames, void* workspace, const rnntOptions& opt);
 }  // namespace rnnt

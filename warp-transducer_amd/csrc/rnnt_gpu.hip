@@ -35,6 +35,8 @@ thread_local AuxStream t_aux;
 
 template rnntStatus_t run_gpu<F32>(const float*, float*, const int*, const int*, const int*, int, int, float*, float*, const float*, void*,
                                    const rnntOptions&, int, int, float, const long long*, long long);
+template rnntStatus_t run_gpu_align<F32>(const float*, const int*, const int*, const int*, int, int, double*, int*, void*,
+                                         const rnntOptions&);
 
 }  // namespace rnnt
 
@@ -173,6 +175,37 @@ rnntStatus_t compute_rnnt_loss_async(const void* activations, void* gradients, c
         return RNNT_STATUS_INVALID_VALUE;
     return run_async(activations, gradients, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch,
                      costs_device, grad_scale_device, workspace, options, dtype_code, 3, -1);
+}
+
+// Best path (Viterbi) through the lattice of compute_rnnt_loss_async: GPU (row statistics, then rnnt_align_kernels.h; enqueue
+// only) or the CPU location (log-probs, host pointers: rnnt_cpu.cpp).
+rnntStatus_t compute_rnnt_align(const void* activations, const int* const flat_labels, const int* const label_lengths,
+                                const int* const input_lengths, int alphabet_size, int minibatch, double* score,
+                                int* frames, void* workspace, rnntOptions options, int dtype_code) {
+    if (bad_args(activations, flat_labels, label_lengths, input_lengths, score, workspace, alphabet_size, minibatch,
+                 options) || (frames == nullptr && options.maxU > 1))
+        return RNNT_STATUS_INVALID_VALUE;
+    if (loc_of(options) == RNNT_CPU) {
+        if (dtype_code == 0)
+            return cpu_rnnt_align_f32(static_cast<const float*>(activations), flat_labels, label_lengths, input_lengths,
+                                      alphabet_size, minibatch, score, frames, workspace, options);
+        if (dtype_code == 1)
+            return cpu_rnnt_align_f64(static_cast<const double*>(activations), flat_labels, label_lengths, input_lengths,
+                                      alphabet_size, minibatch, score, frames, workspace, options);
+        return RNNT_STATUS_INVALID_VALUE;
+    }
+    if (loc_of(options) != RNNT_GPU) return RNNT_STATUS_INVALID_VALUE;
+    switch (dtype_code) {
+        case 0: return run_gpu_align<F32>(static_cast<const float*>(activations), flat_labels, label_lengths, input_lengths,
+                                          alphabet_size, minibatch, score, frames, workspace, options);
+        case 1: return run_gpu_align<F64>(static_cast<const double*>(activations), flat_labels, label_lengths, input_lengths,
+                                          alphabet_size, minibatch, score, frames, workspace, options);
+        case 2: return run_gpu_align<BF16>(static_cast<const uint16_t*>(activations), flat_labels, label_lengths,
+                                           input_lengths, alphabet_size, minibatch, score, frames, workspace, options);
+        case 3: return run_gpu_align<F16>(static_cast<const uint16_t*>(activations), flat_labels, label_lengths,
+                                          input_lengths, alphabet_size, minibatch, score, frames, workspace, options);
+        default: return RNNT_STATUS_INVALID_VALUE;
+    }
 }
 
 // RCCL is looked up at run time: the library links against no collective library.  Which copy matters: an ncclComm_t is

@@ -6,4 +6,6 @@
 namespace rnnt {
 template rnntStatus_t run_gpu<F64>(const double*, double*, const int*, const int*, const int*, int, int, double*, double*, const double*, void*,
                                    const rnntOptions&, int, int, float, const long long*, long long);
+template rnntStatus_t run_gpu_align<F64>(const double*, const int*, const int*, const int*, int, int, double*, int*, void*,
+                                         const rnntOptions&);
 }  // namespace rnnt

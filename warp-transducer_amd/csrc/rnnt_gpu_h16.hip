@@ -8,4 +8,8 @@ template rnntStatus_t run_gpu<BF16>(const uint16_t*, uint16_t*, const int*, cons
                                     const rnntOptions&, int, int, float, const long long*, long long);
 template rnntStatus_t run_gpu<F16>(const uint16_t*, uint16_t*, const int*, const int*, const int*, int, int, float*, float*, const float*, void*,
                                    const rnntOptions&, int, int, float, const long long*, long long);
+template rnntStatus_t run_gpu_align<BF16>(const uint16_t*, const int*, const int*, const int*, int, int, double*, int*, void*,
+                                          const rnntOptions&);
+template rnntStatus_t run_gpu_align<F16>(const uint16_t*, const int*, const int*, const int*, int, int, double*, int*, void*,
+                                         const rnntOptions&);
 }  // namespace rnnt

@@ -12,6 +12,7 @@
 // profile timers) is defined once, in rnnt_gpu.hip; the small non-template helpers are `inline` so that their function-local
 // statics are one object for the whole library.
 #pragma once
+#include "rnnt_align.h"
 #include "rnnt_cpu.h"
 #include "rnnt_host.h"
 
@@ -520,6 +521,24 @@ rnntStatus_t run_gpu(const typename Tag::store* acts, typename Tag::store* grads
     return RNNT_STATUS_SUCCESS;
 }
 
+// Best-path alignment (compute_rnnt_align): the statistics stage exactly as the loss runs it, then the max-plus lattice and the
+// traceback (rnnt_align_kernels.h).  Enqueue only.
+template <typename Tag>
+rnntStatus_t run_gpu_align(const typename Tag::store* acts, const int* labels, const int* label_lengths,
+                           const int* input_lengths, int A, int N, double* score, int* frames, void* workspace,
+                           const rnntOptions& opt) {
+    using C = typename Tag::comp;
+    Plan<C> p;
+    if (!make_plan(p, A, N, opt, workspace, labels, label_lengths, input_lengths, static_cast<C*>(nullptr)))
+        return RNNT_STATUS_INVALID_VALUE;
+    const int vec_ok = (reinterpret_cast<uintptr_t>(acts) % sizeof(typename Tag::store) == 0) ? 1 : 0;
+    launch_row_stats<Tag>(p, acts, vec_ok);
+    if (p.failed) return RNNT_STATUS_EXECUTION_FAILED;
+    const AlignArgs<C> g{p.lp2, p.logz, p.beta, p.llf, p.poison, input_lengths, label_lengths, N, p.maxT, p.maxU, p.Up,
+                         score, frames, p.stream};
+    return launch_align<C>(g) ? RNNT_STATUS_SUCCESS : RNNT_STATUS_EXECUTION_FAILED;
+}
+
 }  // namespace rnnt
 
 namespace rnnt {
@@ -527,15 +546,23 @@ namespace rnnt {
 #ifndef RNNT_GPU_INSTANTIATE_F32
 extern template rnntStatus_t run_gpu<F32>(const float*, float*, const int*, const int*, const int*, int, int, float*, float*, const float*, void*,
                                           const rnntOptions&, int, int, float, const long long*, long long);
+extern template rnntStatus_t run_gpu_align<F32>(const float*, const int*, const int*, const int*, int, int, double*, int*, void*,
+                                                const rnntOptions&);
 #endif
 #ifndef RNNT_GPU_INSTANTIATE_F64
 extern template rnntStatus_t run_gpu<F64>(const double*, double*, const int*, const int*, const int*, int, int, double*, double*, const double*, void*,
                                           const rnntOptions&, int, int, float, const long long*, long long);
+extern template rnntStatus_t run_gpu_align<F64>(const double*, const int*, const int*, const int*, int, int, double*, int*, void*,
+                                                const rnntOptions&);
 #endif
 #ifndef RNNT_GPU_INSTANTIATE_H16
 extern template rnntStatus_t run_gpu<BF16>(const uint16_t*, uint16_t*, const int*, const int*, const int*, int, int, float*, float*, const float*, void*,
                                            const rnntOptions&, int, int, float, const long long*, long long);
 extern template rnntStatus_t run_gpu<F16>(const uint16_t*, uint16_t*, const int*, const int*, const int*, int, int, float*, float*, const float*, void*,
                                           const rnntOptions&, int, int, float, const long long*, long long);
+extern template rnntStatus_t run_gpu_align<BF16>(const uint16_t*, const int*, const int*, const int*, int, int, double*, int*, void*,
+                                                 const rnntOptions&);
+extern template rnntStatus_t run_gpu_align<F16>(const uint16_t*, const int*, const int*, const int*, int, int, double*, int*, void*,
+                                                const rnntOptions&);
 #endif
 }  // namespace rnnt

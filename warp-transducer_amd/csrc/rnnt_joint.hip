@@ -3,9 +3,13 @@
 // unit, hence its own code object: see rnnt_host.h; the 16-bit storage types have theirs (rnnt_joint_impl.h).
 #define RNNT_JOINT_INSTANTIATE_F32 1
 #include "rnnt_joint_impl.h"
+#include "rnnt_align_kernels.h"
 
 namespace rnnt {
-template rnntStatus_t run_gpu_joint<F32>(const float*, const float*, float*, float*, const int*, const int*, const int*, int, int, float*, const float*, void*, const rnntOptions&, int, bool, float);
+// the alignment kernels of every path, both lattice types (rnnt_align.h says why here)
+template bool launch_align<float>(const AlignArgs<float>&);
+template bool launch_align<double>(const AlignArgs<double>&);
+template rnntStatus_t run_gpu_joint<F32>(const float*, const float*, float*, float*, const int*, const int*, const int*, int, int, float*, const float*, void*, const rnntOptions&, int, bool, float, double*, int*);
 }  // namespace rnnt
 
 using namespace rnnt;
@@ -114,6 +118,29 @@ rnntStatus_t compute_rnnt_loss_add_bwd_dt(const void* trans_acts, const void* pr
                                           static_cast<uint16_t*>(trans_grads), static_cast<uint16_t*>(pred_grads), flat_labels,
                                           label_lengths, input_lengths, alphabet_size, minibatch, nullptr, grad_scale_device,
                                           workspace, options, 2, true);
+        default: return RNNT_STATUS_INVALID_VALUE;
+    }
+}
+
+// Best path through the additive joint's lattice: the row maxima and the Z stage of compute_rnnt_loss_add_fwd_dt, then the
+// alignment kernels (rnnt_align_kernels.h).
+rnntStatus_t compute_rnnt_align_add(const void* trans_acts, const void* pred_acts, const int* const flat_labels,
+                                    const int* const label_lengths, const int* const input_lengths, int alphabet_size,
+                                    int minibatch, double* score, int* frames, void* workspace, rnntOptions options,
+                                    int dtype_code) {
+    if (bad_args(trans_acts, flat_labels, label_lengths, input_lengths, score, workspace, alphabet_size, minibatch,
+                 options) || pred_acts == nullptr || (frames == nullptr && options.maxU > 1) || loc_of(options) != RNNT_GPU)
+        return RNNT_STATUS_INVALID_VALUE;
+    switch (dtype_code) {
+        case 0: return run_gpu_joint<F32>(static_cast<const float*>(trans_acts), static_cast<const float*>(pred_acts), nullptr,
+                                          nullptr, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch,
+                                          nullptr, nullptr, workspace, options, 1, false, 0.0f, score, frames);
+        case 2: return run_gpu_joint<BF16>(static_cast<const uint16_t*>(trans_acts), static_cast<const uint16_t*>(pred_acts),
+                                           nullptr, nullptr, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch,
+                                           nullptr, nullptr, workspace, options, 1, false, 0.0f, score, frames);
+        case 3: return run_gpu_joint<F16>(static_cast<const uint16_t*>(trans_acts), static_cast<const uint16_t*>(pred_acts),
+                                          nullptr, nullptr, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch,
+                                          nullptr, nullptr, workspace, options, 1, false, 0.0f, score, frames);
         default: return RNNT_STATUS_INVALID_VALUE;
     }
 }

@@ -4,5 +4,5 @@
 #include "rnnt_joint_impl.h"
 
 namespace rnnt {
-template rnntStatus_t run_gpu_joint<F16>(const uint16_t*, const uint16_t*, uint16_t*, uint16_t*, const int*, const int*, const int*, int, int, float*, const float*, void*, const rnntOptions&, int, bool, float);
+template rnntStatus_t run_gpu_joint<F16>(const uint16_t*, const uint16_t*, uint16_t*, uint16_t*, const int*, const int*, const int*, int, int, float*, const float*, void*, const rnntOptions&, int, bool, float, double*, int*);
 }  // namespace rnnt

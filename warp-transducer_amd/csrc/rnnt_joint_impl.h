@@ -7,6 +7,7 @@
 
 #include <type_traits>
 
+#include "rnnt_align.h"
 #include "rnnt_host.h"
 #include "rnnt_joint_kernels.h"
 #include "rnnt_joint16_kernels.h"
@@ -25,7 +26,8 @@ rnntStatus_t run_gpu_joint(const typename Tag::store* f, const typename Tag::sto
                                   typename Tag::store* dg, const int* labels,
                                   const int* label_lengths, const int* input_lengths, int A, int N,
                                   float* costs_device, const float* grad_scale, void* workspace,
-                                  const rnntOptions& opt, int phases, bool want_grad, float fastemit = 0.0f) {
+                                  const rnntOptions& opt, int phases, bool want_grad, float fastemit = 0.0f,
+                                  double* align_score = nullptr, int* align_frames = nullptr) {
     using S = typename Tag::store;
     // 16-bit storage runs the three GEMMs on the bf16 matrix cores (rnnt_joint16_kernels.h).  fp32 storage does not: with the
     // operands split into THREE bf16 parts (what fp32-class results need: six MFMAs and three roundings per element) the
@@ -47,8 +49,9 @@ rnntStatus_t run_gpu_joint(const typename Tag::store* f, const typename Tag::sto
     const bool training = want_grad;
     std::unique_lock<std::mutex> prof_lock;
     if (g_prof.on.load(std::memory_order_relaxed)) prof_lock = std::unique_lock<std::mutex>(g_prof_mu);
-    const bool prof = prof_prepare(prof_lock.owns_lock());
-    const bool ranges = ranges_prepare();
+    // (an alignment call stops after the Z stage: no stage timers, no marker ranges)
+    const bool prof = align_score == nullptr && prof_prepare(prof_lock.owns_lock());
+    const bool ranges = align_score == nullptr && ranges_prepare();
     static const char* const kStages[4] = {"warprnnt:joint_partition", "warprnnt:lattice", "warprnnt:coefficients",
                                            "warprnnt:joint_gradients"};
     auto mark = [&](int i) {
@@ -141,6 +144,12 @@ rnntStatus_t run_gpu_joint(const typename Tag::store* f, const typename Tag::sto
         p.check();
     }
     mark(1);
+    if (align_score != nullptr) {   // compute_rnnt_align_add: the best path instead of the loss (rnnt_align_kernels.h)
+        if (p.failed) return RNNT_STATUS_EXECUTION_FAILED;
+        const AlignArgs<float> ag{p.lp2, p.logz, p.beta, p.llf, p.poison, input_lengths, label_lengths, N, maxT, maxU, p.Up,
+                                  align_score, align_frames, p.stream};
+        return launch_align<float>(ag) ? RNNT_STATUS_SUCCESS : RNNT_STATUS_EXECUTION_FAILED;
+    }
     if (do_fwd) launch_lattice(p, training);
     mark(2);
     // small vocabularies: the df corrections ride along in the DF GEMM as one-hot operands (3x its
@@ -297,12 +306,12 @@ rnntStatus_t run_gpu_joint(const typename Tag::store* f, const typename Tag::sto
 
 namespace rnnt {
 #ifndef RNNT_JOINT_INSTANTIATE_F32
-extern template rnntStatus_t run_gpu_joint<F32>(const float*, const float*, float*, float*, const int*, const int*, const int*, int, int, float*, const float*, void*, const rnntOptions&, int, bool, float);
+extern template rnntStatus_t run_gpu_joint<F32>(const float*, const float*, float*, float*, const int*, const int*, const int*, int, int, float*, const float*, void*, const rnntOptions&, int, bool, float, double*, int*);
 #endif
 #ifndef RNNT_JOINT_INSTANTIATE_BF16
-extern template rnntStatus_t run_gpu_joint<BF16>(const uint16_t*, const uint16_t*, uint16_t*, uint16_t*, const int*, const int*, const int*, int, int, float*, const float*, void*, const rnntOptions&, int, bool, float);
+extern template rnntStatus_t run_gpu_joint<BF16>(const uint16_t*, const uint16_t*, uint16_t*, uint16_t*, const int*, const int*, const int*, int, int, float*, const float*, void*, const rnntOptions&, int, bool, float, double*, int*);
 #endif
 #ifndef RNNT_JOINT_INSTANTIATE_FP16
-extern template rnntStatus_t run_gpu_joint<F16>(const uint16_t*, const uint16_t*, uint16_t*, uint16_t*, const int*, const int*, const int*, int, int, float*, const float*, void*, const rnntOptions&, int, bool, float);
+extern template rnntStatus_t run_gpu_joint<F16>(const uint16_t*, const uint16_t*, uint16_t*, uint16_t*, const int*, const int*, const int*, int, int, float*, const float*, void*, const rnntOptions&, int, bool, float, double*, int*);
 #endif
 }  // namespace rnnt

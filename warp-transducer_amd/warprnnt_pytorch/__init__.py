@@ -14,7 +14,7 @@ from torch.nn import Module
 from . import warp_rnnt
 from ._checks import certify_inputs, check_contiguous, check_dim, check_type
 
-__all__ = ['rnnt_loss', 'RNNTLoss']
+__all__ = ['rnnt_loss', 'RNNTLoss', 'rnnt_align']
 
 # GPU tensors go through compute_rnnt_loss_async (device costs, no sync) unless
 # WARPRNNT_SYNC_API=1 asks for the reference's host-costs entry point compute_rnnt_loss.
@@ -178,3 +178,50 @@ class RNNTLoss(Module):
             # the kernels only on the GPU (reference __init__.py:95-98).
             acts = torch.nn.functional.log_softmax(acts, -1)
         return self.loss(acts, labels, act_lens, label_lens, self.blank, self.reduction, self.fastemit_lambda, self.validate)
+
+
+def rnnt_align(acts, labels, act_lens, label_lens, blank=0):
+    """Best path (Viterbi) through the lattice `rnnt_loss` sums over (include/rnnt.h, compute_rnnt_align).
+
+    Same inputs as `rnnt_loss` and the same checks (including the lengths' maxima).  Returns ``(score, frames)`` on the
+    device of ``acts``: ``score`` float64 (N,), the natural-log probability of the best path (<= -cost; -inf when
+    every path is forbidden, NaN when the sample's activations hold a NaN); ``frames`` int32 (N, U-1), the frame at
+    which each label is emitted, -1 behind the sample's labels (and everywhere when the score is not finite).  Ties
+    between the two predecessors of a cell go to the blank one: labels are emitted as early as possible.
+    GPU: raw logits of any of the four dtypes, enqueued on the current stream without synchronisation.  CPU:
+    log_softmax, then the CPU location (float32 / float64).  No gradient."""
+    certify_inputs(acts, labels, act_lens, label_lens)
+    lib = warp_rnnt._lib.lib()
+    N, T, U, A = acts.shape
+    with torch.no_grad():
+        if acts.is_cuda:
+            code, esz = warp_rnnt._DT[acts.dtype]
+            warp_rnnt.check_gpu_arguments(acts, labels, act_lens, label_lens)
+            dev = acts.device
+            with torch.cuda.device(dev):
+                score = torch.empty(N, dtype=torch.float64, device=dev)
+                frames = torch.empty((N, U - 1), dtype=torch.int32, device=dev)
+                ws = torch.empty(warp_rnnt._workspace_bytes_cached(T, U, N, esz), dtype=torch.uint8, device=dev)
+                stream = torch.cuda.current_stream(dev)
+                opt = warp_rnnt._options(warp_rnnt._lib.RNNT_GPU, acts, blank, 0, stream.cuda_stream)
+                st = lib.compute_rnnt_align(acts.data_ptr(), labels.data_ptr() if labels.numel() else score.data_ptr(),
+                                            label_lens.data_ptr(), act_lens.data_ptr(), A, N, score.data_ptr(),
+                                            frames.data_ptr() if frames.numel() else None, ws.data_ptr(), opt, code)
+                warp_rnnt._lib.check(st, "compute_rnnt_align")
+                ws.record_stream(stream)
+            return score, frames
+        if acts.dtype not in (torch.float32, torch.float64):
+            raise TypeError("rnnt_align: the CPU location takes float32 or float64 activations, got %s" % acts.dtype)
+        lp = torch.log_softmax(acts, dim=-1).contiguous()
+        code, esz = warp_rnnt._DT[acts.dtype]
+        score = torch.empty(N, dtype=torch.float64)
+        frames = torch.empty((N, U - 1), dtype=torch.int32)
+        ws = torch.empty(warp_rnnt._lib.workspace_bytes(T, U, N, False, esz), dtype=torch.uint8)
+        lab = labels.cpu().contiguous()
+        alen, llen = act_lens.cpu().contiguous(), label_lens.cpu().contiguous()
+        opt = warp_rnnt._options(warp_rnnt._lib.RNNT_CPU, acts, blank, 0, None)
+        st = lib.compute_rnnt_align(lp.data_ptr(), lab.data_ptr() if lab.numel() else score.data_ptr(), llen.data_ptr(),
+                                    alen.data_ptr(), A, N, score.data_ptr(), frames.data_ptr() if frames.numel() else None,
+                                    ws.data_ptr(), opt, code)
+        warp_rnnt._lib.check(st, "compute_rnnt_align")
+        return score, frames

@@ -70,6 +70,9 @@ EXPORTS = {
                                                C.c_int, C.c_int, C.c_float]),
     "compute_rnnt_loss_add_bwd_dt": (C.c_int, [_PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, C.c_int, C.c_int, _PTR,
                                                rnntOptions, C.c_int]),
+    "compute_rnnt_align": (C.c_int, [_PTR, _PTR, _PTR, _PTR, C.c_int, C.c_int, _PTR, _PTR, _PTR, rnntOptions, C.c_int]),
+    "compute_rnnt_align_add": (C.c_int, [_PTR, _PTR, _PTR, _PTR, _PTR, C.c_int, C.c_int, _PTR, _PTR, _PTR, rnntOptions,
+                                         C.c_int]),
     "get_warprnnt_extension_version": (C.c_int, []),
     "rnnt_host_staging": (C.c_int, [C.c_int]),
     "rnnt_host_staging_bytes": (C.c_longlong, []),

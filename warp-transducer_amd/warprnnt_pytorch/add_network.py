@@ -21,7 +21,7 @@ from torch.nn import Module
 from . import _lib, check_contiguous, check_dim, check_type
 from ._checks import check_gpu_arguments
 
-__all__ = ["rnnt_loss_add", "RNNTLossAdd"]
+__all__ = ["rnnt_loss_add", "RNNTLossAdd", "rnnt_align_add"]
 
 _DT = {torch.float32: _lib.DT_F32, torch.bfloat16: _lib.DT_BF16, torch.float16: _lib.DT_F16}
 
@@ -151,3 +151,40 @@ class RNNTLossAdd(Module):
     def forward(self, trans_acts, pred_acts, labels, act_lens, label_lens):
         return rnnt_loss_add(trans_acts, pred_acts, labels, act_lens, label_lens, self.blank, self.reduction,
                              self.fastemit_lambda, self.validate)
+
+
+def rnnt_align_add(trans_acts, pred_acts, labels, act_lens, label_lens, blank=0):
+    """Best path through the additive joint's lattice (compute_rnnt_align_add): `warprnnt_pytorch.rnnt_align` of
+    ``trans_acts.unsqueeze(2) + pred_acts.unsqueeze(1)`` without forming that tensor.  Same inputs and checks as
+    `rnnt_loss_add`; returns ``(score float64 (B,), frames int32 (B, U))`` on the device, enqueued on the current
+    stream without synchronisation.  No gradient."""
+    _certify(trans_acts, pred_acts, labels, act_lens, label_lens)
+    lib = _lib.lib()
+    B, T, V = trans_acts.shape
+    U = pred_acts.shape[1]
+    dev = trans_acts.device
+    with torch.no_grad(), torch.cuda.device(dev):
+        score = torch.empty(B, dtype=torch.float64, device=dev)
+        frames = torch.empty((B, U - 1), dtype=torch.int32, device=dev)
+        ws = torch.empty(_workspace_bytes_add_cached(T, U, B), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        opt = _lib.rnntOptions(loc=_lib.RNNT_GPU, num_threads=0, stream=stream.cuda_stream, blank_label=int(blank),
+                               maxT=T, maxU=U, batch_first=True)
+        lab_ptr = labels.data_ptr() if labels.numel() else score.data_ptr()   # maxU == 1: never read
+        st = lib.compute_rnnt_align_add(trans_acts.data_ptr(), pred_acts.data_ptr(), lab_ptr, label_lens.data_ptr(),
+                                        act_lens.data_ptr(), V, B, score.data_ptr(),
+                                        frames.data_ptr() if frames.numel() else None, ws.data_ptr(), opt,
+                                        _DT[trans_acts.dtype])
+        _lib.check(st, "compute_rnnt_align_add")
+        ws.record_stream(stream)
+    return score, frames
+
+
+_WS_ADD = {}
+
+
+def _workspace_bytes_add_cached(T, U, B):
+    n = _WS_ADD.get((T, U, B))
+    if n is None:
+        n = _WS_ADD[(T, U, B)] = _lib.workspace_bytes_add(T, U, B)
+    return n
