@@ -322,10 +322,9 @@ OTHER = {
             "rnnt::loss_sum_kernel<float>": "compute_rnnt_loss_sharded: tests/test_gpu_sharded_rccl.py",
             "rnnt::loss_sum_kernel<double>": "compute_rnnt_loss_sharded: tests/test_gpu_sharded_rccl.py"},
 }
-# Code objects out of scope: the additive joint's (rnnt_joint*.hip, recognised by their joint_* kernels).  RNNT_DEV-only
-# forms (row_stats_kernel<.., 2|8, ..>, row_stats_block_kernel<.., false, ..>, grad_flat_kernel<.., 0, 1|4, 0>) are not in a
-# release build at all; the inventory fails if one appears there.
-EXCLUDED_OBJECTS = "additive joint (rnnt_joint.hip, rnnt_joint_bf16.hip, rnnt_joint_fp16.hip)"
+# RNNT_DEV-only forms (row_stats_kernel<.., 2|8, ..>, row_stats_block_kernel<.., false, ..>, grad_flat_kernel<.., 0, 1|4, 0>) are
+# not in a release build at all; the inventory fails if one appears there.  The additive joint's objects (rnnt_joint*.hip) have
+# their table in tests/joint_forms.py.
 
 
 def expected_inventory():

@@ -1,7 +1,8 @@
-"""No GPU: the kernels of the materialised path in the release build's code objects (warp-transducer_amd/lib/libwarprnnt.so)
-against the committed table of tests/kernel_forms.py.  A kernel the build holds without a row -- a new form no case reaches --
+"""No GPU: the kernels of the release build's code objects (warp-transducer_amd/lib/libwarprnnt.so) against the committed
+tables of tests/kernel_forms.py (materialised path) and tests/joint_forms.py (additive joint and alignment).  A kernel the build holds without a row -- a new form no case reaches --
 fails, and so does a row naming a kernel the build no longer has.  Every row's case must reach its kernel under the release
-rules (kernel_forms.predict); tests/test_gpu_kernel_forms.py runs the cases and checks on the GPU that they do."""
+rules (kernel_forms.predict, joint_forms.predict_joint); tests/test_gpu_kernel_forms.py and tests/test_gpu_joint_forms.py run
+the cases and check on the GPU that they do."""
 import os
 import shutil
 import struct
@@ -9,6 +10,7 @@ import subprocess
 
 import pytest
 
+from tests import joint_forms as J
 from tests import kernel_forms as K
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,9 +56,11 @@ def kernel_names(elf, tmp_path, readelf, cxxfilt):
 
 
 def classify(names):
-    """Which object of the release build a code object is: f32 / f64 / h16 (materialised path), joint (out of scope)."""
+    """Which object of the release build a code object is: f32 / f64 / h16 (materialised path), joint_f32 / joint_bf16 /
+    joint_f16 (additive joint, by the store tag of its DF kernels)."""
     if any(n.split("<")[0].split("::")[-1].startswith("joint_") for n in names):
-        return "joint"
+        objs = [obj for obj, tag, _ in J.JSTORES.values() if any(n.startswith("rnnt::joint_df_kernel<%s," % tag) for n in names)]
+        return objs[0] if len(objs) == 1 else "unknown"
     for obj, tag in (("f32", "rnnt::F32"), ("f64", "rnnt::F64"), ("h16", "rnnt::BF16")):
         if any(n.startswith("rnnt::grad_flat_kernel<%s," % tag) for n in names):
             return obj
@@ -76,14 +80,18 @@ def build_inventory(tmp_path_factory):
         names = kernel_names(elf, tmp, readelf, cxxfilt)
         obj = classify(names)
         assert obj != "unknown", sorted(names)[:10]
-        if obj != "joint":
-            assert obj not in inv, "two code objects look like the %s translation unit" % obj
-            inv[obj] = names
+        assert obj not in inv, "two code objects look like the %s translation unit" % obj
+        inv[obj] = names
     return inv
 
 
 def test_materialised_objects_present(build_inventory):
-    assert set(build_inventory) == set(K.OBJECTS), sorted(build_inventory)
+    assert set(K.OBJECTS) <= set(build_inventory), sorted(build_inventory)
+
+
+def test_joint_objects_present(build_inventory):
+    """Exactly the three materialised and the three additive-joint objects, each recognised by its store tag."""
+    assert set(build_inventory) == set(K.OBJECTS) | set(J.JOBJECTS), sorted(build_inventory)
 
 
 @pytest.mark.parametrize("obj", sorted(K.OBJECTS))
@@ -131,3 +139,63 @@ def test_required_cases_are_present():
     lin = {c["name"] for c in K.CASES.values() if c["N"] == "cus//2"}
     log = {c["name"] for c in K.CASES.values() if c["N"] == "cus//2+1"}
     assert len(lin) == len(log) == len(K.STORES)
+
+
+# ----------------------------------------------------------------------------- the additive joint and the alignment kernels
+@pytest.mark.parametrize("obj", sorted(J.JOBJECTS))
+def test_joint_every_kernel_has_a_row_and_every_row_a_kernel(build_inventory, obj):
+    built = build_inventory[obj]
+    table = J.expected_inventory()[obj]
+    missing_rows = sorted(built - set(table))
+    stale_rows = sorted(set(table) - built)
+    assert not missing_rows, "kernels of %s without a row in tests/joint_forms.py: %s" % (J.JOBJECTS[obj], missing_rows)
+    assert not stale_rows, "rows naming kernels %s no longer holds: %s" % (J.JOBJECTS[obj], stale_rows)
+
+
+def test_joint_every_row_is_reached_by_its_case():
+    """joint_forms.FORMS against the release rules of run_gpu_joint (256 compute units); tests/test_gpu_joint_forms.py repeats
+    this with the device's own count and observes the launches."""
+    reach = J.predicted_rows(256)
+    for obj, kernel, case in J.FORMS:
+        assert case in J.JCASES, (kernel, case)
+        assert case in reach.get((obj, kernel), []), "case %s does not reach %s under the release rules" % (case, kernel)
+    rows = {(o, k) for o, k, _ in J.FORMS}
+    assert set(reach) <= rows, sorted(set(reach) - rows)
+    forms = [(o, k) for o, k, _ in J.FORMS]
+    assert len(forms) == len(set(forms))
+    # a form the table calls unreachable is reached by no case
+    unreachable = {(obj, k) for obj, ks in J.expected_inventory().items() for k, why in ks.items() if why.startswith("unreachable")}
+    assert not unreachable & set(reach), sorted(unreachable & set(reach))
+
+
+def test_joint_rules_restate_the_source():
+    """The constants predict_joint restates -- kJointZSmallA, the A >= 512 gates of the 16-bit matrix-core forms, the vocabulary
+    split, the split DF / DG bounds, the release Tune defaults -- against the headers: a retune fails here before a GPU run."""
+    assert J.source_constants() == J.restated_constants()
+
+
+def test_joint_required_cases_are_present():
+    """The boundaries the matrix must keep, whatever else changes: both sides of each threshold of run_gpu_joint."""
+    sh = {n: K.case_shape(c, 256) for n, c in J.JCASES.items()}
+    train = [n for n, c in J.JCASES.items() if c["entry"] not in ("align", "align_add")]
+    for d in J.JSTORES:
+        mine = [n for n in train if J.JCASES[n]["dtype"] == d]
+        a = {sh[n][3] for n in mine}
+        assert {J.JOINT_Z_SMALL_A, J.JOINT_Z_SMALL_A + 1, 63, 64} <= a, (d, sorted(a))
+        assert {480, 488, 992, 1000} <= a                                    # ceil(A / 32) = 15 / 16, 31 / 32
+        tiles = {sh[n][0] * ((sh[n][1] + 31) // 32) * ((sh[n][2] + 31) // 32) for n in mine}
+        assert {1023, 1024, 4095, 4096} <= tiles
+        assert {48, 49, 63, 64} <= {sh[n][2] for n in mine}
+        assert {63, 64, 511, 512} <= {sh[n][1] for n in mine}
+        if d != "f32":
+            assert {504, 512} <= a
+        for entry in ("guard", "masked32", "far"):
+            assert any(J.JCASES[n].get("data") == entry for n in mine), (d, entry)
+        assert any(J.JCASES[n]["N"] == "cus//2" for n in mine) and any(J.JCASES[n]["N"] == "cus//2+1" for n in mine)
+    entries = {(c["entry"], c["dtype"]) for c in J.JCASES.values()}
+    assert {("add", "f32"), ("twophase", "f32"), ("fastemit", "f32"), ("dt", "f32"), ("dt", "bf16"), ("dt", "f16")} <= entries
+    assert {("align_add", d) for d in J.JSTORES} <= entries and {("align", d) for d in K.STORES} <= entries
+    al = [n for n, c in J.JCASES.items() if c["entry"] in ("align", "align_add")]
+    assert {64, 65, 1024} <= {sh[n][2] for n in al}
+    assert any(sh[n][2] == 1024 and (sh[n][1] + 1024 - 1) > J.ALIGN_LDS_WORDS // J.ALIGN_MAX_WAVES for n in al)  # several chunks
+    assert any(J.JCASES[n].get("data") == "planted" and sh[n][2] == 1024 for n in al)
