@@ -3,7 +3,9 @@
     pip install . --no-build-isolation          # builds libwarprnnt.so with hipcc (gfx950) and the extension module with g++
     WARP_RNNT_PATH=/dir/with/libwarprnnt.so pip install . --no-build-isolation      # a prebuilt library, as the reference asks for
 
-The installed package is self-contained: warprnnt_pytorch/{*.py, _warp_rnnt_ext*.so, lib/libwarprnnt.so, include/rnnt.h};
+The installed package is self-contained: warprnnt_pytorch/{*.py, _warp_rnnt_ext*.so, lib/libwarprnnt.so, include/rnnt.h}, and
+lib/libwarprnnt_pruned.so + include/rnnt_pruned.h for warprnnt_pytorch.pruned when that library was built (or lies beside a
+WARP_RNNT_PATH library);
 no sys.path edits, no environment variables at run time (a WARP_RNNT_PATH naming ANOTHER library at run time is honoured by switching to
 the ctypes loader: the compiled module is linked to the library it was built with).
 torch must be importable at build time (--no-build-isolation), exactly as for the reference's setup.py, which imports it.
@@ -47,12 +49,19 @@ class build_native(build_py):
             if not os.path.exists(src):
                 raise SystemExit("Could not find libwarprnnt.so in %s (WARP_RNNT_PATH)" % prebuilt)
         else:
-            subprocess.run(["make", "-j3", "-C", os.path.join(ROOT, "warp-transducer_amd"), "lib/libwarprnnt.so"], check=True)
+            subprocess.run(["make", "-j3", "-C", os.path.join(ROOT, "warp-transducer_amd"), "lib/libwarprnnt.so",
+                            "lib/libwarprnnt_pruned.so"], check=True)
             src = os.path.join(ROOT, "warp-transducer_amd", "lib", "libwarprnnt.so")
         shutil.copy2(src, os.path.join(lib_out, "libwarprnnt.so"))
+        # the pruned loss's library (warprnnt_pytorch.pruned loads it on first use): beside libwarprnnt.so when it was built or
+        # handed over; without it the package installs and everything else works
+        pruned = os.path.join(os.path.dirname(src), "libwarprnnt_pruned.so")
+        if os.path.exists(pruned):
+            shutil.copy2(pruned, os.path.join(lib_out, "libwarprnnt_pruned.so"))
         inc_out = os.path.join(pkg_out, "include")
         os.makedirs(inc_out, exist_ok=True)
         shutil.copy2(os.path.join(ROOT, "include", "rnnt.h"), os.path.join(inc_out, "rnnt.h"))
+        shutil.copy2(os.path.join(ROOT, "include", "rnnt_pruned.h"), os.path.join(inc_out, "rnnt_pruned.h"))
         spec = importlib.util.spec_from_file_location("_warprnnt_build_ext", os.path.join(PKG_SRC, "build_ext.py"))
         be = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(be)
@@ -61,7 +70,8 @@ class build_native(build_py):
 
 def _build_in_tree():
     if not os.environ.get("WARP_RNNT_PATH"):
-        subprocess.run(["make", "-j3", "-C", os.path.join(ROOT, "warp-transducer_amd"), "lib/libwarprnnt.so"], check=True)
+        subprocess.run(["make", "-j3", "-C", os.path.join(ROOT, "warp-transducer_amd"), "lib/libwarprnnt.so",
+                        "lib/libwarprnnt_pruned.so"], check=True)
     subprocess.run([sys.executable, os.path.join(PKG_SRC, "build_ext.py")], check=True)
 
 

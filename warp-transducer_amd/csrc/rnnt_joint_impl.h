@@ -15,6 +15,100 @@
 namespace rnnt {
 
 // ----------------------------------------------------------------------------- additive joint
+// Stage 1 of the additive joint: row maxima of f and g, then the partition-function GEMM with the log-prob epilogue -- lp2 / log Z
+// of every cell, what the lattice reads.  `training`: the row-maximum / prep kernels also zero the correction sums of the
+// gradient GEMMs.  run_gpu_joint's forward phase; also the first stage of compute_rnnt_prune_ranges_add (rnnt_pruned.h).
+template <typename Tag>
+static void launch_joint_partition(Plan<float>& p, const typename Tag::store* f, const typename Tag::store* g, bool training) {
+    using S = typename Tag::store;
+    constexpr bool k16 = sizeof(typename Tag::store) == 2;
+    const int jbits = tune().j16;
+    const int N = p.N, A = p.A, maxT = p.maxT, maxU = p.maxU;
+    const int *labels = p.labels, *input_lengths = p.input_lengths, *label_lengths = p.label_lengths;
+    // rows made of whole 16-byte packets (row-maximum kernel) and 4-element loads aligned (Z kernel)
+    const bool vec = (A % static_cast<int>(16 / sizeof(S)) == 0) &&
+                     ((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(g)) & 15u) == 0;
+    const int tilesT = (maxT + 31) / 32, tilesU = (maxU + 31) / 32, tiles = tilesT * tilesU;
+    {   // row maxima, then the partition-function GEMM with the log-prob epilogue (a block: its vocabulary split S shadows the store type)
+        const long long rows = static_cast<long long>(N) * (maxT + maxU);
+        const bool per_block = static_cast<size_t>(A) * sizeof(S) >= 12288;       // long rows: a block per row
+        const bool per_lanes = A <= 64;                                            // short rows: eight lanes per row
+        const dim3 rgrid(static_cast<unsigned>(per_block ? rows : per_lanes ? (rows + 31) / 32 : (rows + 3) / 4));
+        // vocabulary slices per tile: few tiles and a long contraction -> split it over 4 or 8 wavefronts
+        const long long all_tiles = static_cast<long long>(N) * tiles;
+        const int nchunk = (A + 31) / 32;
+        int S = (all_tiles >= 4096 || nchunk < 16) ? 1 : ((all_tiles < 1024 && nchunk >= 32) ? 8 : 4);
+        if (tune().jzs == 1 || tune().jzs == 4 || tune().jzs == 8) S = tune().jzs;
+        const bool small = S == 1 && A <= kJointZSmallA && tune().jzs != 1;
+        // sampled row references + guard (rnnt_joint_kernels.h): no row-maximum pass in front of the Z kernel; the exact
+        // pair runs behind it only when a row tripped the guard
+        const bool sampled = !small && A >= 64 && tune().jsamp != 0;
+        const bool z16 = k16 && (jbits & 4) != 0 && !small && A % 8 == 0 && A >= 512 &&
+                         ((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(g)) & 15u) == 0;
+        (void)z16;
+        int* const gate = reinterpret_cast<int*>(p.rowmax + rows + 1);
+        static std::atomic<int> call_counter{1};
+        const int seq = call_counter.fetch_add(1, std::memory_order_relaxed);
+        float* side0 = training ? p.side : nullptr;
+        const unsigned nside = static_cast<unsigned>(p.side_bytes / sizeof(float));
+    #define RNNT_JMAX(VV, WW, SIDE, GATE)                                                                           \
+    hipLaunchKernelGGL((joint_rowmax_kernel<Tag, VV, WW>), rgrid, dim3(256), 0, p.stream, f, g, input_lengths,       \
+                       label_lengths, p.rowmax, maxT, maxU, A, N, SIDE, nside, GATE, seq)
+    #define RNNT_JMAX_ALL(SIDE, GATE)                                                                               \
+        do {                                                                                                    \
+            if (per_block) { if (vec) RNNT_JMAX(true, 4, SIDE, GATE); else RNNT_JMAX(false, 4, SIDE, GATE); }   \
+            else if (per_lanes) RNNT_JMAX(false, 0, SIDE, GATE);                                                \
+            else { if (vec) RNNT_JMAX(true, 1, SIDE, GATE); else RNNT_JMAX(false, 1, SIDE, GATE); }             \
+        } while (0)
+    #define RNNT_JZ(SS, VV, SAMP, GATE)                                                                              \
+    hipLaunchKernelGGL((joint_z_kernel<Tag, SS, VV, SAMP>), SS == 1 ? dim3(((tiles + 3) / 4 + 7) / 8 * 8, N) : dim3(xcd_shared_grid(1, tiles, N)),               \
+                       dim3(SS == 1 ? 256 : SS * 64), 0, p.stream, f, g, p.rowmax, labels, input_lengths,        \
+                       label_lengths, p.lp2, p.logz, maxT, maxU, p.Up, A, p.blank, tilesU, tiles, N, GATE, seq, p.poison)
+    #define RNNT_JZ16(SS, SAMP, GATE)                                                                                \
+    hipLaunchKernelGGL((joint_z16_kernel<Tag, SS, SAMP>), SS == 1 ? dim3(((tiles + 3) / 4 + 7) / 8 * 8, N) : dim3(xcd_shared_grid(1, tiles, N)),    \
+                       dim3(SS == 1 ? 256 : SS * 64), 0, p.stream, f, g, p.rowmax, labels, input_lengths,        \
+                       label_lengths, p.lp2, p.logz, maxT, maxU, p.Up, A, p.blank, tilesU, tiles, N, GATE, seq, p.poison)
+    #define RNNT_JZ_ALL(SAMP, GATE)                                                                                  \
+        do {                                                                                                    \
+            if constexpr (k16) {                                                      \
+                if (z16) {     /* bf16 storage on the bf16 matrix cores (rnnt_joint16_kernels.h) */              \
+                    if (S == 8) RNNT_JZ16(8, SAMP, GATE); else if (S == 4) RNNT_JZ16(4, SAMP, GATE);            \
+                    else RNNT_JZ16(1, SAMP, GATE);                                                              \
+                    break;                                                                                      \
+                }                                                                                               \
+            }                                                                                                   \
+            if (S == 8) { if (vec) RNNT_JZ(8, true, SAMP, GATE); else RNNT_JZ(8, false, SAMP, GATE); }          \
+            else if (S == 4) { if (vec) RNNT_JZ(4, true, SAMP, GATE); else RNNT_JZ(4, false, SAMP, GATE); }     \
+            else { if (vec) RNNT_JZ(1, true, SAMP, GATE); else RNNT_JZ(1, false, SAMP, GATE); }                 \
+        } while (0)
+        if (sampled) {
+            const unsigned pgrid = (nside + 255) / 256 > 0 ? (nside + 255) / 256 : 1;
+            hipLaunchKernelGGL(joint_prep_kernel<0>, dim3(pgrid), dim3(256), 0, p.stream, p.rowmax, side0, nside, gate, seq,
+                               static_cast<unsigned>(rows));
+            RNNT_JZ_ALL(true, gate);
+            RNNT_JMAX_ALL(static_cast<float*>(nullptr), gate);           // the exact pair: returns at once unless the gate is raised
+            RNNT_JZ_ALL(false, gate);
+        } else {
+            int* const no_gate = nullptr;                                // the row-maximum pass always runs
+            RNNT_JMAX_ALL(side0, no_gate);
+            p.check();
+            if (small)
+                hipLaunchKernelGGL((joint_z_small_kernel<Tag>), dim3(((tiles + 3) / 4 + 7) / 8 * 8, N), dim3(256),
+                                   4 * joint_z_small_slice(A) * sizeof(float), p.stream, f, g, p.rowmax, labels,
+                                   input_lengths, label_lengths, p.lp2, p.logz, maxT, maxU, p.Up, A, p.blank, tilesU,
+                                   tiles, N, p.poison, joint_z_small_slice(A));
+            else
+                RNNT_JZ_ALL(false, no_gate);
+        }
+    #undef RNNT_JMAX
+    #undef RNNT_JMAX_ALL
+    #undef RNNT_JZ
+    #undef RNNT_JZ_ALL
+    #undef RNNT_JZ16
+        p.check();
+    }
+}
+
 // f (N,maxT,A) + g (N,maxU,A) -> costs, df, dg without the (N,T,U,A) tensor (rnnt_joint_kernels.h):
 // the two streaming stages are replaced, lattice and coefficients are the same launches as above.
 // Enqueue only: device costs, no host copy, no synchronisation.  Storage of f, g, df, dg by tag (fp32 / bf16 / fp16),
@@ -60,89 +154,9 @@ rnntStatus_t run_gpu_joint(const typename Tag::store* f, const typename Tag::sto
     };
 
     const int maxT = p.maxT, maxU = p.maxU;
-    // rows made of whole 16-byte packets (row-maximum kernel) and 4-element loads aligned (Z kernel)
-    const bool vec = (A % static_cast<int>(16 / sizeof(S)) == 0) &&
-                     ((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(g)) & 15u) == 0;
-    const int tilesT = (maxT + 31) / 32, tilesU = (maxU + 31) / 32, tiles = tilesT * tilesU;
+    const int tilesT = (maxT + 31) / 32, tilesU = (maxU + 31) / 32;
     mark(0);
-    if (do_fwd) {   // row maxima, then the partition-function GEMM with the log-prob epilogue
-        const long long rows = static_cast<long long>(N) * (maxT + maxU);
-        const bool per_block = static_cast<size_t>(A) * sizeof(S) >= 12288;       // long rows: a block per row
-        const bool per_lanes = A <= 64;                                            // short rows: eight lanes per row
-        const dim3 rgrid(static_cast<unsigned>(per_block ? rows : per_lanes ? (rows + 31) / 32 : (rows + 3) / 4));
-        // vocabulary slices per tile: few tiles and a long contraction -> split it over 4 or 8 wavefronts
-        const long long all_tiles = static_cast<long long>(N) * tiles;
-        const int nchunk = (A + 31) / 32;
-        int S = (all_tiles >= 4096 || nchunk < 16) ? 1 : ((all_tiles < 1024 && nchunk >= 32) ? 8 : 4);
-        if (tune().jzs == 1 || tune().jzs == 4 || tune().jzs == 8) S = tune().jzs;
-        const bool small = S == 1 && A <= kJointZSmallA && tune().jzs != 1;
-        // sampled row references + guard (rnnt_joint_kernels.h): no row-maximum pass in front of the Z kernel; the exact
-        // pair runs behind it only when a row tripped the guard
-        const bool sampled = !small && A >= 64 && tune().jsamp != 0;
-        const bool z16 = k16 && (jbits & 4) != 0 && !small && A % 8 == 0 && A >= 512 &&
-                         ((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(g)) & 15u) == 0;
-        (void)z16;
-        int* const gate = reinterpret_cast<int*>(p.rowmax + rows + 1);
-        static std::atomic<int> call_counter{1};
-        const int seq = call_counter.fetch_add(1, std::memory_order_relaxed);
-        float* side0 = training ? p.side : nullptr;
-        const unsigned nside = static_cast<unsigned>(p.side_bytes / sizeof(float));
-#define RNNT_JMAX(VV, WW, SIDE, GATE)                                                                           \
-    hipLaunchKernelGGL((joint_rowmax_kernel<Tag, VV, WW>), rgrid, dim3(256), 0, p.stream, f, g, input_lengths,       \
-                       label_lengths, p.rowmax, maxT, maxU, A, N, SIDE, nside, GATE, seq)
-#define RNNT_JMAX_ALL(SIDE, GATE)                                                                               \
-        do {                                                                                                    \
-            if (per_block) { if (vec) RNNT_JMAX(true, 4, SIDE, GATE); else RNNT_JMAX(false, 4, SIDE, GATE); }   \
-            else if (per_lanes) RNNT_JMAX(false, 0, SIDE, GATE);                                                \
-            else { if (vec) RNNT_JMAX(true, 1, SIDE, GATE); else RNNT_JMAX(false, 1, SIDE, GATE); }             \
-        } while (0)
-#define RNNT_JZ(SS, VV, SAMP, GATE)                                                                              \
-    hipLaunchKernelGGL((joint_z_kernel<Tag, SS, VV, SAMP>), SS == 1 ? dim3(((tiles + 3) / 4 + 7) / 8 * 8, N) : dim3(xcd_shared_grid(1, tiles, N)),               \
-                       dim3(SS == 1 ? 256 : SS * 64), 0, p.stream, f, g, p.rowmax, labels, input_lengths,        \
-                       label_lengths, p.lp2, p.logz, maxT, maxU, p.Up, A, p.blank, tilesU, tiles, N, GATE, seq, p.poison)
-#define RNNT_JZ16(SS, SAMP, GATE)                                                                                \
-    hipLaunchKernelGGL((joint_z16_kernel<Tag, SS, SAMP>), SS == 1 ? dim3(((tiles + 3) / 4 + 7) / 8 * 8, N) : dim3(xcd_shared_grid(1, tiles, N)),    \
-                       dim3(SS == 1 ? 256 : SS * 64), 0, p.stream, f, g, p.rowmax, labels, input_lengths,        \
-                       label_lengths, p.lp2, p.logz, maxT, maxU, p.Up, A, p.blank, tilesU, tiles, N, GATE, seq, p.poison)
-#define RNNT_JZ_ALL(SAMP, GATE)                                                                                  \
-        do {                                                                                                    \
-            if constexpr (k16) {                                                      \
-                if (z16) {     /* bf16 storage on the bf16 matrix cores (rnnt_joint16_kernels.h) */              \
-                    if (S == 8) RNNT_JZ16(8, SAMP, GATE); else if (S == 4) RNNT_JZ16(4, SAMP, GATE);            \
-                    else RNNT_JZ16(1, SAMP, GATE);                                                              \
-                    break;                                                                                      \
-                }                                                                                               \
-            }                                                                                                   \
-            if (S == 8) { if (vec) RNNT_JZ(8, true, SAMP, GATE); else RNNT_JZ(8, false, SAMP, GATE); }          \
-            else if (S == 4) { if (vec) RNNT_JZ(4, true, SAMP, GATE); else RNNT_JZ(4, false, SAMP, GATE); }     \
-            else { if (vec) RNNT_JZ(1, true, SAMP, GATE); else RNNT_JZ(1, false, SAMP, GATE); }                 \
-        } while (0)
-        if (sampled) {
-            const unsigned pgrid = (nside + 255) / 256 > 0 ? (nside + 255) / 256 : 1;
-            hipLaunchKernelGGL(joint_prep_kernel<0>, dim3(pgrid), dim3(256), 0, p.stream, p.rowmax, side0, nside, gate, seq,
-                               static_cast<unsigned>(rows));
-            RNNT_JZ_ALL(true, gate);
-            RNNT_JMAX_ALL(static_cast<float*>(nullptr), gate);           // the exact pair: returns at once unless the gate is raised
-            RNNT_JZ_ALL(false, gate);
-        } else {
-            int* const no_gate = nullptr;                                // the row-maximum pass always runs
-            RNNT_JMAX_ALL(side0, no_gate);
-            p.check();
-            if (small)
-                hipLaunchKernelGGL((joint_z_small_kernel<Tag>), dim3(((tiles + 3) / 4 + 7) / 8 * 8, N), dim3(256),
-                                   4 * joint_z_small_slice(A) * sizeof(float), p.stream, f, g, p.rowmax, labels,
-                                   input_lengths, label_lengths, p.lp2, p.logz, maxT, maxU, p.Up, A, p.blank, tilesU,
-                                   tiles, N, p.poison, joint_z_small_slice(A));
-            else
-                RNNT_JZ_ALL(false, no_gate);
-        }
-#undef RNNT_JMAX
-#undef RNNT_JMAX_ALL
-#undef RNNT_JZ
-#undef RNNT_JZ_ALL
-#undef RNNT_JZ16
-        p.check();
-    }
+    if (do_fwd) launch_joint_partition<Tag>(p, f, g, training);
     mark(1);
     if (align_score != nullptr) {   // compute_rnnt_align_add: the best path instead of the loss (rnnt_align_kernels.h)
         if (p.failed) return RNNT_STATUS_EXECUTION_FAILED;
