@@ -1,0 +1,99 @@
+"""The kernel forms of libwarprnnt_hat.so (csrc/rnnt_hat.hip, rnnt_hat_f64.hip, rnnt_hat_h16.hip): which kernels its three code
+objects hold, the release rules that pick them (a restatement of run_hat / launch_hat_stats / launch_lattice /
+launch_hat_coef / launch_hat_grad, csrc/rnnt_hat_impl.h and csrc/rnnt_host.h), and one case per form that reaches it -- the
+counterpart of tests/tdt_forms.py.  tests/test_hat_cpu.py checks the table against the built code objects;
+tests/test_gpu_hat.py runs every case and checks that exactly the predicted kernels ran.
+
+A case: dtype, N, T, U (= maxU), A, blank; `off` = byte offset of the logits and gradients from a 16-byte boundary (the
+element-wise gradient form).  The blank sits at column 0, at A - 1 and at interior columns that are not the first lane of a
+16-byte packet."""
+
+OBJECTS = {"f32": "rnnt_hat.hip", "f64": "rnnt_hat_f64.hip", "h16": "rnnt_hat_h16.hip"}
+# dtype -> (object, store tag, lattice type, element bytes)
+STORES = {"f32": ("f32", "rnnt::F32", "float", 4), "f64": ("f64", "rnnt::F64", "double", 8),
+          "bf16": ("h16", "rnnt::BF16", "float", 2), "f16": ("h16", "rnnt::F16", "float", 2)}
+STAGES = ("stats", "lattice", "coef", "grad")
+
+
+def stage_of(name):
+    base = name.split("<")[0].split("::")[-1]
+    return {"hat_stats_kernel": "stats", "lattice_kernel": "lattice", "lattice_lin_kernel": "lattice",
+            "coef_kernel": "coef", "coef_cell_kernel": "coef", "hat_grad_kernel": "grad",
+            "hat_grad_elem_kernel": "grad"}.get(base)
+
+
+def stats_group(row_bytes):
+    """launch_hat_stats: lanes per row."""
+    return 4 if row_bytes <= 256 else 16 if row_bytes <= 4096 else 64
+
+
+def lat_stride(U):
+    return (U + 7) & ~7
+
+
+def predict(case, cus):
+    """{stage: set of kernel names} the release rules launch for `case` on a device of `cus` compute units (a training
+    call: both lattice directions)."""
+    obj, tag, lat, esz = STORES[case["dtype"]]
+    N, U = case["N"], case["U"]
+    up = lat_stride(U)
+    if up <= 64 and lat == "float" and 2 * N <= cus:
+        lattice = "rnnt::lattice_lin_kernel<0>"
+    elif up <= 64:
+        lattice = "rnnt::lattice_kernel<%s, 1, 1>" % lat
+    elif up <= 256:
+        lattice = "rnnt::lattice_kernel<%s, 8, 1>" % lat
+    elif up <= 512:
+        lattice = "rnnt::lattice_kernel<%s, 4, 2>" % lat
+    else:
+        lattice = "rnnt::lattice_kernel<%s, 8, 2>" % lat
+    coef = "rnnt::coef_cell_kernel<%s>" % lat if U <= 48 else "rnnt::coef_kernel<%s, false>" % lat
+    grad = "rnnt::hat_grad_kernel<%s>" % tag if case.get("off", 0) % 16 == 0 else "rnnt::hat_grad_elem_kernel<%s>" % tag
+    return {"stats": {"rnnt::hat_stats_kernel<%s, %d>" % (tag, stats_group(case["A"] * esz))},
+            "lattice": {lattice}, "coef": {coef}, "grad": {grad}}
+
+
+def object_of(case):
+    return STORES[case["dtype"]][0]
+
+
+def _case(name, dtype, N, T, U, A, blank, **kw):
+    return dict(name=name, dtype=dtype, N=N, T=T, U=U, A=A, blank=blank, **kw)
+
+
+def _cases():
+    cs = []
+    for d in ("f32", "f64", "bf16", "f16"):
+        cs += [_case(d + "_a5", d, 4, 9, 7, 5, 2),                        # 4 lanes per row; linear lattice (fp64: <1, 1>)
+               _case(d + "_a300", d, 3, 8, 6, 300, 299),                   # 16 lanes per row, blank last
+               _case(d + "_a1025", d, 3, 8, 6, 1025, 0),                   # 16 lanes per row, unaligned 2 KB+ rows, blank first
+               _case(d + "_a5003", d, 3, 6, 5, 5003, 2501),                # 64 lanes per row, unaligned rows, blank interior
+               _case(d + "_off", d, 3, 6, 5, 63, 17, off=STORES[d][3]),    # element-wise gradient
+               _case(d + "_lat81", d, 3, 30, 100, 6, 5),                   # lattice <8, 1>, tiled coefficients
+               _case(d + "_lat42", d, 3, 12, 300, 5, 3),                   # lattice <4, 2>
+               _case(d + "_lat82", d, 3, 10, 600, 5, 1)]                   # lattice <8, 2>
+        if d != "f64":
+            cs.append(_case(d + "_lat11", d, 300, 6, 5, 5, 1))             # more blocks than compute units: lattice <1, 1>
+    return cs
+
+
+CASES = {c["name"]: c for c in _cases()}
+UNREACHABLE = {}
+
+
+def predicted_rows(cus=256):
+    """{(object, kernel): [cases]} the release rules reach with CASES on a device of `cus` compute units."""
+    rows = {}
+    for name, c in CASES.items():
+        for ks in predict(c, cus).values():
+            for k in ks:
+                rows.setdefault((object_of(c), k), []).append(name)
+    return rows
+
+
+def expected_inventory(cus=256):
+    """{object: set of kernels} the three code objects must hold exactly."""
+    inv = {o: set() for o in OBJECTS}
+    for (obj, k) in list(predicted_rows(cus)) + list(UNREACHABLE):
+        inv[obj].add(k)
+    return inv

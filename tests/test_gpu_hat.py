@@ -1,0 +1,496 @@
+"""-m gpu: the Hybrid Autoregressive Transducer loss (include/rnnt_hat.h, libwarprnnt_hat.so).
+
+Every case of tests/hat_forms.py runs through the C-ABI under torch.profiler: exactly the kernels its release rules predict run,
+stage by stage.  Costs are compared with the fp64 autograd reference of tests/hat_ref.py at rtol = atol = 1e-5 (1e-9 for fp64),
+gradients per element at oracle.grad_bound with mag = |ref| and, for the blank and label columns, the row's |ref| sum.  Ragged
+lengths (one sample with T_b = 1, one with L_b = 0), NaN in every padding row (never read) and gradient buffers that start as
+NaN (padding must come back as exact zeros).  A negative control compares against the plain RNN-T loss and must fail.  Then
+the call forms, the invalid arguments, the non-finite cases of the header, |z_blank| = 80, the cross-check against
+RNNTLoss(hat_log_probs(z)), the autograd module, a HIP-graph capture, one bf16 tensor past 2^31 elements, and c3- / c4-shaped
+problems."""
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as O
+from tests import hat_forms as F
+from tests import hat_ref as R
+from tests.test_gpu_kernel_forms import _cus, _profiled
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+_TORCH = {"f32": torch.float32, "f64": torch.float64, "bf16": torch.bfloat16, "f16": torch.float16}
+_CODE = {"f32": 0, "f64": 1, "bf16": 2, "f16": 3}
+_NAME = {v: k for k, v in _TORCH.items()}
+_COST_TOL = {"f64": 1e-9, "f32": 1e-5, "bf16": 1e-5, "f16": 1e-5}
+
+
+def _hat():
+    from warprnnt_pytorch import hat
+    return hat
+
+
+def _opt(T, U, blank=0, stream=None):
+    from warprnnt_pytorch import _lib
+    s = stream if stream is not None else torch.cuda.current_stream()
+    return _lib.rnntOptions(loc=_lib.RNNT_GPU, num_threads=0, stream=s.cuda_stream, blank_label=blank, maxT=T, maxU=U,
+                            batch_first=True)
+
+
+def _lengths(N, T, U, rng):
+    tl = rng.integers(1, T + 1, size=N).astype(np.int32)
+    ll = rng.integers(0, U, size=N).astype(np.int32)
+    tl[0], ll[0] = T, U - 1
+    if N > 1:
+        tl[1] = 1
+    if N > 2:
+        ll[2] = 0
+    return tl, ll
+
+
+def _place(values, off, dtype):
+    """A device tensor of `values` `off` bytes past a 16-byte boundary inside a larger NaN buffer."""
+    esz = torch.finfo(dtype).bits // 8
+    n = values.numel()
+    buf = torch.full((n + 32 // esz,), float("nan"), dtype=dtype, device=DEV)
+    base = (-buf.data_ptr() % 16) // esz
+    v = buf[base + off // esz: base + off // esz + n].view(values.shape)
+    v.copy_(values)
+    assert v.data_ptr() % 16 == off
+    return v
+
+
+def _labels(rng, N, U, A, blank):
+    """Labels in [0, A) without the blank."""
+    lab = rng.integers(0, A - 1, size=(N, U - 1)).astype(np.int32)
+    return lab + (lab >= blank)
+
+
+def _problem(name, dtype, N, T, U, A, blank, rng=None, lengths=None, scale=2.0):
+    rng = rng or np.random.default_rng(zlib.crc32(name.encode()))
+    tl, ll = lengths if lengths is not None else _lengths(N, T, U, rng)
+    labels = _labels(rng, N, U, A, blank)
+    x = torch.tensor(rng.standard_normal((N, T, U, A)) * scale, dtype=torch.float32).to(_TORCH[dtype])
+    mask = R.in_lattice_mask((N, T, U), tl, ll)
+    x[torch.tensor(~mask)] = float("nan")
+    return x, labels, tl, ll, mask
+
+
+def _dev(*arrs):
+    return [torch.tensor(np.ascontiguousarray(a), device=DEV) for a in arrs]
+
+
+def call(x, labels, tl, ll, blank=0, form="one", scale=None, grads=None, stream=None):
+    """One C-ABI call form -> (status, costs, grads or None).  form: one | two | inplace | score | host."""
+    h = _hat()
+    N, T, U, A = x.shape
+    code = _CODE[_NAME[x.dtype]]
+    lab, ttl, tll = _dev(labels if labels.size else np.zeros((N, 1), np.int32), tl, ll)
+    cdt = torch.float64 if x.dtype == torch.float64 else torch.float32
+    costs = torch.full((N,), float("nan"), dtype=cdt, device=DEV)
+    ws = torch.empty(h.workspace_bytes(T, U, N, code), dtype=torch.uint8, device=DEV)
+    opt = _opt(T, U, blank, stream)
+    lib = h.lib()
+    if grads is None and form not in ("score", "inplace", "host"):
+        grads = torch.full_like(x, float("nan"))
+    if form in ("one", "score", "inplace", "host"):
+        g = None if form == "score" else (x if form == "inplace" else grads)
+        gp = g.data_ptr() if g is not None else None
+        if form == "host":
+            hc = np.full(N, np.nan, dtype=np.float64 if cdt == torch.float64 else np.float32)
+            st = lib.compute_hat_loss(x.data_ptr(), gp, lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N,
+                                      hc.ctypes.data, ws.data_ptr(), opt, code)
+            return st, hc, (None if g is None else g.double().cpu().numpy())
+        st = lib.compute_hat_loss(x.data_ptr(), gp, lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N,
+                                  costs.data_ptr(), ws.data_ptr(), opt, code)
+        (stream or torch.cuda.current_stream()).synchronize()
+        return st, costs.cpu().numpy(), (None if g is None else g.double().cpu().numpy())
+    st = lib.compute_hat_loss_fwd(x.data_ptr(), lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N, costs.data_ptr(),
+                                  ws.data_ptr(), opt, code, 1)
+    assert st == 0
+    sc = None if scale is None else torch.tensor(scale, dtype=cdt, device=DEV)
+    st = lib.compute_hat_loss_bwd(x.data_ptr(), grads.data_ptr(), sc.data_ptr() if sc is not None else None, A, N,
+                                  ws.data_ptr(), opt, code)
+    torch.cuda.synchronize()
+    return st, costs.cpu().numpy(), grads.double().cpu().numpy()
+
+
+def _reference(x, labels, tl, ll, blank=0, weights=None, plain=False):
+    xr = torch.nan_to_num(x.double().cpu(), nan=0.0).numpy()
+    return R.hat_autograd(xr, labels, tl, ll, blank, weights, plain)
+
+
+def _mag(ref, labels, ll, blank):
+    """The size of the terms of every gradient element: |ref|, and for the blank and label columns the row's |ref| sum
+    (they carry the subtracted posteriors)."""
+    mag = np.abs(ref).copy()
+    rs = np.abs(ref).sum(-1)
+    mag[..., blank] = np.maximum(mag[..., blank], rs)
+    N, T, U, _ = ref.shape
+    for b in range(N):
+        for u in range(min(U, int(ll[b]))):
+            lab = int(labels[b, u])
+            mag[b, :, u, lab] = np.maximum(mag[b, :, u, lab], rs[b, :, u])
+    return mag
+
+
+def _check(dtype, got_c, got_g, ref_c, ref_g, mask, labels, ll, blank=0, scale=None, what=""):
+    w = np.ones(len(ref_c)) if scale is None else np.asarray(scale, np.float64)
+    tol = _COST_TOL[dtype]
+    print(what, "max |dcost| = %.3e" % np.abs(got_c - ref_c).max())
+    assert np.allclose(got_c, ref_c, rtol=tol, atol=tol), (what, got_c, ref_c)
+    if got_g is None:
+        return
+    assert not got_g[~mask].any(), (what, "padding must be exact zeros")
+    worst = 0.0
+    for b in range(len(ref_c)):
+        m = mask[b]
+        ref = ref_g[b:b + 1] * w[b]
+        mag = _mag(ref, labels[b:b + 1], ll[b:b + 1], blank)[0][m]
+        # (oracle.py: 16-bit storage on lattices of more than ~500 diagonals passes rel=1e-3 -- the fp32 lattice's own error)
+        rel = 1e-3 if dtype in ("bf16", "f16") and got_g.shape[1] + labels.shape[1] > 500 else None
+        r = O.grad_check(got_g[b][m], ref[0][m], mag, _TORCH[dtype], rel=rel)
+        worst = max(worst, r["max_err_over_quantum"])
+        assert r["passed"], ("%s sample %d" % (what, b), r)
+    print(what, "max gradient error / bound = %.3f" % worst)
+
+
+# ----------------------------------------------------------------------------- every form of tests/hat_forms.py
+@pytest.mark.parametrize("name", sorted(F.CASES))
+def test_hat_form(name):
+    case = F.CASES[name]
+    cus = _cus()
+    N, T, U, A, blank, dtype = case["N"], case["T"], case["U"], case["A"], case["blank"], case["dtype"]
+    x, labels, tl, ll, mask = _problem(name, dtype, N, T, U, A, blank)
+    off = case.get("off", 0)
+    xv = _place(x.to(DEV), off, x.dtype)
+    gv = _place(torch.full_like(x, float("nan")).to(DEV), off, x.dtype)
+    (st, c, g), names = _profiled(lambda: call(xv, labels, tl, ll, blank, "one", grads=gv))
+    assert st == 0
+    want = F.predict(case, cus)
+    seen = {s: set() for s in F.STAGES}
+    for n in names:
+        s = F.stage_of(n)
+        if s is not None:
+            seen[s].add(n)
+    assert seen == want, (name, seen, want)
+    rc, rg = _reference(x, labels, tl, ll, blank)
+    _check(dtype, c, g, rc, rg, mask, labels, ll, blank, what=name)
+
+
+def test_every_hat_row_reached_on_this_device():
+    rows = F.predicted_rows(_cus())
+    for obj, ks in F.expected_inventory().items():
+        for k in ks:
+            assert (obj, k) in rows or (obj, k) in F.UNREACHABLE, (obj, k)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64", "bf16"])
+def test_negative_control_plain_rnnt_is_refused(dtype):
+    """The same comparison against the loss with the blank column left inside the label softmax (plain RNN-T) must fail:
+    the check cannot pass on the wrong loss."""
+    N, T, U, A, blank = 4, 9, 7, 40, 13
+    x, labels, tl, ll, mask = _problem("neg_" + dtype, dtype, N, T, U, A, blank)
+    st, c, g = call(x.to(DEV), labels, tl, ll, blank, "one")
+    assert st == 0
+    rc, rg = _reference(x, labels, tl, ll, blank)
+    _check(dtype, c, g, rc, rg, mask, labels, ll, blank, what="hat")
+    pc, pg = _reference(x, labels, tl, ll, blank, plain=True)
+    with pytest.raises(AssertionError):
+        _check(dtype, c, None, pc, pg, mask, labels, ll, blank, what="plain costs")
+    with pytest.raises(AssertionError):
+        _check(dtype, rc, g, rc, pg, mask, labels, ll, blank, what="plain gradients")
+
+
+# ----------------------------------------------------------------------------- call forms and edge cases
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_call_forms_agree(dtype):
+    N, T, U, A, blank = 5, 7, 9, 130, 77
+    x, labels, tl, ll, mask = _problem("forms_" + dtype, dtype, N, T, U, A, blank)
+    xd = x.to(DEV)
+    st, c1, g1 = call(xd, labels, tl, ll, blank, "one")
+    assert st == 0
+    scale = (0.5 + 0.25 * np.arange(N)).astype(np.float64)
+    st, c2, g2 = call(xd, labels, tl, ll, blank, "two", scale=scale)
+    assert st == 0 and np.array_equal(c1, c2)
+    rc, rg = _reference(x, labels, tl, ll, blank, weights=scale)
+    _check(dtype, c2, g2, rc, rg, mask, labels, ll, blank, what="two-phase")
+    g1s = g1 * scale[:, None, None, None]
+    assert np.allclose(g2, g1s, rtol=1e-2 if dtype == "bf16" else 1e-6, atol=1e-6)
+    xi = xd.clone()
+    st, c3, g3 = call(xi, labels, tl, ll, blank, "inplace")
+    assert st == 0 and np.array_equal(c1, c3) and np.array_equal(g3, g1)
+    st, c4, _ = call(xd, labels, tl, ll, blank, "score")
+    assert st == 0 and np.array_equal(c1, c4)
+    st, c5, g5 = call(xd, labels, tl, ll, blank, "host", grads=torch.full_like(xd, float("nan")))
+    assert st == 0 and np.array_equal(c1.astype(c5.dtype), c5) and np.array_equal(g5, g1)
+
+
+def test_invalid_arguments():
+    N, T, U, A = 2, 4, 3, 5
+    x, labels, tl, ll, _ = _problem("inv", "f32", N, T, U, A, 0)
+    xd = torch.nan_to_num(x.to(DEV))
+    # lengths that do not fit the tensor: the cost marker -> INVALID_VALUE with host costs; the other sample is computed
+    st, c, _ = call(xd, labels, np.array([T + 1, T], np.int32), ll, 0, "host")
+    assert st == 2
+    st, c, g = call(xd, labels, np.array([T, T], np.int32), np.array([U, 1], np.int32), 0, "one")
+    assert st == 0 and np.isnan(c[0]) and np.isfinite(c[1]) and not g[0].any()
+    # blank outside the columns, a single column, maxU past the limit, a dtype code, overlapping tensors
+    for blank in (A, -1):
+        st, _, _ = call(xd, labels, tl, ll, blank, "one")
+        assert st == 2
+    st, _, _ = call(torch.zeros((1, 2, 1, 1), device=DEV), np.zeros((1, 0), np.int32), np.array([2], np.int32),
+                    np.array([0], np.int32), 0, "one")
+    assert st == 2
+    h = _hat()
+    import ctypes as C
+    n = C.c_size_t(0)
+    assert h.lib().get_workspace_size_hat(4, 1025, 1, 0, C.byref(n)) == 2
+    assert h.lib().get_workspace_size_hat(4, 3, 1, 4, C.byref(n)) == 2
+    assert h.lib().get_workspace_size_hat(4, 3, 1, 0, C.byref(n)) == 0 and n.value > 0
+    buf = torch.zeros(2 * xd.numel(), device=DEV)
+    a = buf[:xd.numel()].view(xd.shape).copy_(xd)
+    st, _, _ = call(a, labels, tl, ll, 0, "one", grads=buf[4:4 + xd.numel()].view(xd.shape))
+    assert st == 2
+
+
+def test_label_equal_to_blank_poisons_its_sample_only():
+    N, T, U, A, blank = 3, 5, 4, 9, 4
+    rng = np.random.default_rng(21)
+    tl, ll = np.array([5, 4, 5], np.int32), np.array([3, 2, 1], np.int32)
+    x, labels, tl, ll, mask = _problem("lab", "f32", N, T, U, A, blank, rng=rng, lengths=(tl, ll))
+    labels[1, 1] = blank               # inside L_1 = 2: poisons sample 1
+    labels[2, 2] = blank               # behind L_2 = 1: never looked at
+    st, c, g = call(x.to(DEV), labels, tl, ll, blank, "one")
+    assert st == 0
+    assert np.isnan(c[1]) and np.isnan(g[1][mask[1]]).all() and not g[~mask].any()
+    keep = [0, 2]
+    rc, rg = _reference(x[keep], labels[keep], tl[keep], ll[keep], blank)
+    _check("f32", c[keep], g[keep], rc, rg, mask[keep], labels[keep], ll[keep], blank, what="unpoisoned")
+    from warprnnt_pytorch.hat import rnnt_loss_hat
+    with pytest.raises(ValueError, match="blank"):
+        rnnt_loss_hat(torch.nan_to_num(x).to(DEV), *_dev(labels, tl, ll), blank=blank, reduction="none")
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64", "bf16"])
+def test_non_finite_inputs(dtype):
+    """NaN in an in-lattice row (label or blank column), a +inf label logit, all label logits -inf: that sample only.
+    z_blank = -inf / +inf are limits: finite cost while a path is left, +inf when none is."""
+    N, T, U, A, blank = 8, 5, 3, 11, 6
+    rng = np.random.default_rng(5)
+    tl, ll = np.full(N, 4, np.int32), np.full(N, 2, np.int32)
+    tl[0] = 5
+    x, labels, tl, ll, mask = _problem("nf_" + dtype, dtype, N, T, U, A, blank, rng=rng, lengths=(tl, ll))
+    inf = float("inf")
+    x[1, 1, 0, 3] = float("nan")                                 # a NaN label logit
+    x[2, 2, 1, blank] = float("nan")                             # a NaN blank logit
+    x[3, 0, 1, 8] = inf                                          # a +inf label logit
+    x[4, 0, 1, :] = -inf
+    x[4, 0, 1, blank] = 0.5                                      # all label logits -inf
+    x[5, 1, 1, blank] = -inf                                     # b = 0 in one cell: paths around it remain
+    x[5, 2, 0, blank] = inf                                      # b = 1 in one cell
+    x[6, 3, 2, blank] = -inf                                     # b = 0 in the terminal cell: no path
+    x[7, :, 0:2, blank] = inf                                    # b = 1 wherever a label must be emitted: no path
+    st, c, g = call(x.to(DEV), labels, tl, ll, blank, "one")
+    assert st == 0
+    for b in (1, 2, 3, 4):
+        assert np.isnan(c[b]) and np.isnan(g[b][mask[b]]).all(), (b, c)
+    for b in (6, 7):
+        assert np.isposinf(c[b]), (b, c)
+    assert not g[~mask].any()
+    keep = [0, 5]
+    # the reference takes the limits at z_blank = -200 / +200: autograd through logsigmoid(+-inf) is NaN, and sigmoid(+-200)
+    # differs from 0 / 1 by e^-200, far below every bound here
+    xr = x[keep].clone()
+    xr[..., blank] = torch.nan_to_num(xr[..., blank].float(), nan=0.0).clamp(-200.0, 200.0).to(xr.dtype)
+    rc, rg = _reference(xr, labels[keep], tl[keep], ll[keep], blank)
+    assert np.isfinite(rc).all()
+    _check(dtype, c[keep], g[keep], rc, rg, mask[keep], labels[keep], ll[keep], blank, what="limits")
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_blank_logit_of_magnitude_80(dtype):
+    """|z_blank| = 80: log(1 - sigmoid(80)) is -inf in fp32 arithmetic, -softplus(80) is -80."""
+    N, T, U, A, blank = 2, 2, 2, 7, 3
+    tl, ll = np.array([2, 2], np.int32), np.array([1, 1], np.int32)
+    x, labels, tl, ll, mask = _problem("z80_" + dtype, dtype, N, T, U, A, blank, lengths=(tl, ll), scale=1.0)
+    x[0, :, :, blank] = torch.tensor([[80.0, -80.0], [-80.0, 80.0]]).to(x.dtype)
+    x[1, :, :, blank] = torch.tensor([[-80.0, 80.0], [80.0, -80.0]]).to(x.dtype)
+    st, c, g = call(x.to(DEV), labels, tl, ll, blank, "one")
+    assert st == 0 and np.isfinite(c).all() and c.max() > 70, c     # (sample 1 has to pay one 80 at least)
+    rc, rg = _reference(x, labels, tl, ll, blank)
+    assert np.isfinite(rc).all() and np.isfinite(rg).all()
+    _check(dtype, c, g, rc, rg, mask, labels, ll, blank, what="z80")
+
+
+def test_closed_form_single_cell():
+    """T = 1, L = 0: cost = softplus(-z_blank)."""
+    z = np.array([-3.0, 0.25, 7.0])
+    x = torch.zeros((3, 1, 1, 4), dtype=torch.float64)
+    x[:, 0, 0, 2] = torch.tensor(z)
+    st, c, _ = call(x.to(DEV), np.zeros((3, 0), np.int32), np.ones(3, np.int32), np.zeros(3, np.int32), 2, "score")
+    assert st == 0 and np.allclose(c, np.log1p(np.exp(-z)), rtol=1e-12)
+
+
+def test_cross_check_against_rnntloss_of_hat_log_probs():
+    """HATLoss(z) against RNNTLoss(hat_log_probs(z)) with autograd through the transform, fp64, on the GPU."""
+    from warprnnt_pytorch import RNNTLoss
+    from warprnnt_pytorch.hat import HATLoss, hat_log_probs
+    N, T, U, A, blank = 4, 12, 8, 37, 9
+    rng = np.random.default_rng(17)
+    tl, ll = _lengths(N, T, U, rng)
+    tl[1] = 3
+    labels = _labels(rng, N, U, A, blank)
+    x = torch.tensor(rng.standard_normal((N, T, U, A)) * 2, dtype=torch.float64, device=DEV)
+    lab, ttl, tll = _dev(labels, tl, ll)
+    xa = x.clone().requires_grad_()
+    la = HATLoss(blank=blank, reduction="none")(xa, lab, ttl, tll)
+    la.sum().backward()
+    xb = x.clone().requires_grad_()
+    lb = RNNTLoss(blank=blank, reduction="none")(hat_log_probs(xb, blank), lab, ttl, tll)
+    lb.sum().backward()
+    assert torch.allclose(la, lb, rtol=1e-9, atol=1e-9), (la, lb)
+    mask = R.in_lattice_mask((N, T, U), tl, ll)
+    ga, gb = xa.grad.cpu().numpy(), xb.grad.cpu().numpy()
+    assert not ga[~mask].any()
+    O.assert_grads(ga[mask], gb[mask], _mag(gb, labels, ll, blank)[mask], torch.float64, what="cross-check")
+
+
+# ----------------------------------------------------------------------------- autograd
+@pytest.mark.parametrize("reduction", ["none", "sum", "mean"])
+def test_autograd_reductions(reduction):
+    from warprnnt_pytorch.hat import HATLoss
+    N, T, U, A, blank = 3, 6, 4, 11, 10
+    rng = np.random.default_rng(3)
+    tl, ll = np.array([6, 5, 3], np.int32), np.array([3, 2, 1], np.int32)
+    x, labels, tl, ll, mask = _problem("ag", "f32", N, T, U, A, blank, rng=rng, lengths=(tl, ll))
+    x = torch.nan_to_num(x)
+    xd = x.to(DEV).requires_grad_()
+    loss = HATLoss(blank=blank, reduction=reduction)(xd, *_dev(labels, tl, ll))
+    go = torch.tensor([0.7, -1.3, 2.0][:loss.numel()], device=DEV).view(loss.shape)
+    (loss * go).sum().backward()
+    w = go.detach().cpu().numpy().reshape(-1)
+    w = np.broadcast_to(w, (N,)) / (N if reduction == "mean" else 1)
+    rc, rg = _reference(x, labels, tl, ll, blank, weights=w)
+    want = {"none": rc, "sum": rc.sum(keepdims=True), "mean": rc.mean(keepdims=True)}[reduction]
+    assert np.allclose(loss.detach().cpu().numpy(), want, rtol=1e-5)
+    got = xd.grad.double().cpu().numpy()
+    assert not got[~mask].any()
+    O.assert_grads(got[mask], rg[mask], _mag(rg, labels, ll, blank)[mask], torch.float32)
+
+
+def test_gradcheck_fp64():
+    from warprnnt_pytorch.hat import rnnt_loss_hat
+    N, T, U, A, blank = 2, 4, 3, 5, 2
+    rng = np.random.default_rng(2)
+    labels = _labels(rng, N, U, A, blank)
+    lab, ttl, tll = _dev(labels, np.array([4, 3], np.int32), np.array([2, 1], np.int32))
+    x = torch.tensor(rng.standard_normal((N, T, U, A)), dtype=torch.float64, device=DEV, requires_grad=True)
+    assert torch.autograd.gradcheck(lambda z: rnnt_loss_hat(z, lab, ttl, tll, blank, "none"), (x,), eps=1e-6, atol=1e-6,
+                                    nondet_tol=1e-12)
+
+
+def test_cpu_tensors_are_refused():
+    from warprnnt_pytorch.hat import rnnt_loss_hat
+    x = torch.zeros(1, 2, 2, 5)
+    with pytest.raises(ValueError, match="GPU"):
+        rnnt_loss_hat(x, torch.ones(1, 1, dtype=torch.int32), torch.tensor([2], dtype=torch.int32),
+                      torch.tensor([1], dtype=torch.int32))
+
+
+def test_hip_graph_capture_and_replay():
+    """Forward + backward captured once (one branch), replayed on new logits."""
+    from warprnnt_pytorch.hat import rnnt_loss_hat
+    N, T, U, A, blank = 3, 8, 5, 33, 32
+    rng = np.random.default_rng(11)
+    tl, ll = np.array([8, 6, 4], np.int32), np.array([4, 0, 2], np.int32)
+    labels = _labels(rng, N, U, A, blank)
+    lab, ttl, tll = _dev(labels, tl, ll)
+    static_x = torch.zeros((N, T, U, A), device=DEV, requires_grad=True)
+    h = _hat()
+    h.lib()
+    h.workspace_bytes(T, U, N, 0)
+
+    def step():
+        static_x.grad = None
+        loss = rnnt_loss_hat(static_x, lab, ttl, tll, blank, "sum", validate=False)
+        loss.backward()
+        return loss
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            step()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    static_x.grad = None
+    with torch.cuda.graph(graph):
+        loss = rnnt_loss_hat(static_x, lab, ttl, tll, blank, "sum", validate=False)
+        loss.backward()
+    grad = static_x.grad
+    for seed in (1, 2):
+        xn = np.random.default_rng(seed).standard_normal((N, T, U, A)).astype(np.float32)
+        with torch.no_grad():
+            static_x.copy_(torch.tensor(xn))
+        graph.replay()
+        torch.cuda.synchronize()
+        rc, rg = R.hat_autograd(xn, labels, tl, ll, blank)
+        assert abs(loss.item() - rc.sum()) < 1e-5 * rc.sum()
+        mask = R.in_lattice_mask((N, T, U), tl, ll)
+        got = grad.double().cpu().numpy()
+        assert not got[~mask].any()
+        O.assert_grads(got[mask], rg[mask], _mag(rg, labels, ll, blank)[mask], torch.float32, what="replay %d" % seed)
+
+
+# ----------------------------------------------------------------------------- c3- and c4-shaped problems
+@pytest.mark.parametrize("shape", ["c3", "c4"])
+def test_benchmark_shapes(shape):
+    """Two samples at the c3 shape (T = 150, U = 21, A = 5000) and the c4 shape (T = 1500, U = 301, A = 50: lattice_kernel
+    with 1800 anti-diagonals), fp32, ragged."""
+    T, U, A, blank = (150, 21, 5000, 0) if shape == "c3" else (1500, 301, 50, 49)
+    N = 2
+    rng = np.random.default_rng(7)
+    tl, ll = np.array([T, (3 * T) // 4], np.int32), np.array([U - 1, (5 * U) // 6], np.int32)
+    x, labels, tl, ll, mask = _problem(shape, "f32", N, T, U, A, blank, rng=rng, lengths=(tl, ll), scale=1.0)
+    st, c, g = call(x.to(DEV), labels, tl, ll, blank, "one")
+    assert st == 0
+    rc, rg = _reference(x, labels, tl, ll, blank)
+    assert np.isfinite(rc).all()
+    _check("f32", c, g, rc, rg, mask, labels, ll, blank, what=shape)
+
+
+# ----------------------------------------------------------------------------- 64-bit addressing
+def test_bf16_in_place_past_2_31_elements():
+    """bf16 in place, N T U A > 2^31 elements: the last sample's in-lattice rows lie past element 2^31."""
+    N, T, U, A, blank = 5, 64, 65, 130001, 70000
+    E = N * T * U * A
+    assert E > 2 ** 31 and 4 * T * U * A > 2 ** 31 - 3 * T * U * A
+    need = 2 * E + (1 << 30)
+    free = torch.cuda.mem_get_info(0)[0]
+    if free < need:
+        print("SKIPPED: %d bytes of device memory free, the tensor past 2^31 elements needs %d" % (free, need))
+        pytest.skip("device memory is short")
+    tl, ll = np.array([1, 2, 3, 2, 4], np.int32), np.array([0, 1, 2, 1, 3], np.int32)
+    rng = np.random.default_rng(13)
+    labels = _labels(rng, N, U, A, blank)
+    g = torch.Generator(device=DEV).manual_seed(1)
+    x = torch.randn((N, T, U, A), generator=g, device=DEV, dtype=torch.bfloat16)
+    small = torch.zeros((N, 4, 4, A), dtype=torch.float64)
+    for b in range(N):
+        small[b, :tl[b], :ll[b] + 1] = x[b, :tl[b], :ll[b] + 1].double().cpu()
+    st, c, _ = call(x, labels, tl, ll, blank, "inplace")
+    assert st == 0
+    rc, rg = R.hat_autograd(small.numpy(), labels[:, :3], tl, ll, blank)
+    assert np.allclose(c, rc, rtol=1e-5, atol=1e-5), (c, rc)
+    for b in range(N):
+        assert x[b, tl[b]:].count_nonzero().item() == 0
+        assert x[b, :tl[b], ll[b] + 1:].count_nonzero().item() == 0
+        got = x[b, :tl[b], :ll[b] + 1].double().cpu().numpy()
+        ref = rg[b, :tl[b], :ll[b] + 1]
+        O.assert_grads(got, ref, np.maximum(np.abs(ref), np.abs(ref).sum(-1, keepdims=True)), torch.bfloat16,
+                       what="sample %d" % b)

@@ -1,0 +1,98 @@
+// rnnt_hat.hip -- libwarprnnt_hat.so: the C entry points of include/rnnt_hat.h and the fp32 instantiation (run_hat<F32>);
+// rnnt_hat_impl.h has the driver, rnnt_hat_kernels.h the kernels.
+#define RNNT_HAT_INSTANTIATE_F32 1
+#include "rnnt_hat_impl.h"
+
+namespace rnnt {
+// the state rnnt_host.h declares (the main library's copies are hidden inside it; this library never turns them on)
+Profile g_prof;
+std::mutex g_prof_mu;
+Ranges g_ranges;
+
+template rnntStatus_t run_hat<F32>(const float*, float*, const float*, const int*, const int*, const int*, int, int, float*,
+                                   float*, void*, const rnntOptions&, int, bool);
+}  // namespace rnnt
+
+using namespace rnnt;
+
+namespace {
+// Host memory (pageable or pinned) or device memory?  The one-call entry copies host costs behind its last kernel.
+bool is_device_pointer(const void* p) {
+    hipPointerAttribute_t attr;
+    const bool dev = hipPointerGetAttributes(&attr, p) == hipSuccess &&
+                     (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged);
+    (void)hipGetLastError();                       // (the query of a pageable pointer reports an error: not ours)
+    return dev;
+}
+
+rnntStatus_t dispatch(const void* acts, void* grads, const void* scale, const int* labels, const int* label_lengths,
+                      const int* input_lengths, int A, int N, void* costs_dev, void* costs_host, void* workspace,
+                      const rnntOptions& o, int dtype_code, int phases, bool want_grad) {
+    switch (dtype_code) {
+        case 0:
+            return run_hat<F32>(static_cast<const float*>(acts), static_cast<float*>(grads), static_cast<const float*>(scale),
+                                labels, label_lengths, input_lengths, A, N, static_cast<float*>(costs_dev),
+                                static_cast<float*>(costs_host), workspace, o, phases, want_grad);
+        case 1:
+            return run_hat<F64>(static_cast<const double*>(acts), static_cast<double*>(grads),
+                                static_cast<const double*>(scale), labels, label_lengths, input_lengths, A, N,
+                                static_cast<double*>(costs_dev), static_cast<double*>(costs_host), workspace, o, phases,
+                                want_grad);
+        case 2:
+            return run_hat<BF16>(static_cast<const uint16_t*>(acts), static_cast<uint16_t*>(grads),
+                                 static_cast<const float*>(scale), labels, label_lengths, input_lengths, A, N,
+                                 static_cast<float*>(costs_dev), static_cast<float*>(costs_host), workspace, o, phases,
+                                 want_grad);
+        case 3:
+            return run_hat<F16>(static_cast<const uint16_t*>(acts), static_cast<uint16_t*>(grads),
+                                static_cast<const float*>(scale), labels, label_lengths, input_lengths, A, N,
+                                static_cast<float*>(costs_dev), static_cast<float*>(costs_host), workspace, o, phases,
+                                want_grad);
+        default: return RNNT_STATUS_INVALID_VALUE;
+    }
+}
+}  // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+rnntStatus_t get_workspace_size_hat(int maxT, int maxU, int minibatch, int dtype_code, size_t* size_bytes) {
+    if (minibatch <= 0 || maxT <= 0 || maxU <= 0 || maxU > 1024 || size_bytes == nullptr || dtype_code < 0 ||
+        dtype_code > 3)
+        return RNNT_STATUS_INVALID_VALUE;
+    *size_bytes = make_layout(maxT, maxU, minibatch, dtype_code == 1 ? 8 : 4, false).total;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t compute_hat_loss(const void* activations, void* gradients, const int* flat_labels, const int* label_lengths,
+                              const int* input_lengths, int alphabet_size, int minibatch, void* costs, void* workspace,
+                              rnntOptions options, int dtype_code) {
+    if (bad_args(activations, flat_labels, label_lengths, input_lengths, costs, workspace, alphabet_size, minibatch,
+                 options) || loc_of(options) != RNNT_GPU)
+        return RNNT_STATUS_INVALID_VALUE;
+    const bool dev = is_device_pointer(costs);
+    return dispatch(activations, gradients, nullptr, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch,
+                    dev ? costs : nullptr, dev ? nullptr : costs, workspace, options, dtype_code, 3, gradients != nullptr);
+}
+
+rnntStatus_t compute_hat_loss_fwd(const void* activations, const int* flat_labels, const int* label_lengths,
+                                  const int* input_lengths, int alphabet_size, int minibatch, void* costs_device,
+                                  void* workspace, rnntOptions options, int dtype_code, int prepare_backward) {
+    if (bad_args(activations, flat_labels, label_lengths, input_lengths, costs_device, workspace, alphabet_size, minibatch,
+                 options) || loc_of(options) != RNNT_GPU)
+        return RNNT_STATUS_INVALID_VALUE;
+    return dispatch(activations, nullptr, nullptr, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch,
+                    costs_device, nullptr, workspace, options, dtype_code, 1, prepare_backward != 0);
+}
+
+rnntStatus_t compute_hat_loss_bwd(const void* activations, void* gradients, const void* grad_scale_device,
+                                  int alphabet_size, int minibatch, void* workspace, rnntOptions options, int dtype_code) {
+    if (activations == nullptr || gradients == nullptr || workspace == nullptr || alphabet_size <= 0 || minibatch <= 0 ||
+        options.maxT <= 0 || options.maxU <= 0 || loc_of(options) != RNNT_GPU)
+        return RNNT_STATUS_INVALID_VALUE;
+    return dispatch(activations, gradients, grad_scale_device, nullptr, nullptr, nullptr, alphabet_size, minibatch, nullptr,
+                    nullptr, workspace, options, dtype_code, 2, true);
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

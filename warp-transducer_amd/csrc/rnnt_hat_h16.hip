@@ -1,0 +1,11 @@
+// rnnt_hat_h16.hip -- the HAT loss for bf16 and fp16 storage (fp32 lattice), a code object of its own (rnnt_hat_impl.h says
+// why).
+#define RNNT_HAT_INSTANTIATE_H16 1
+#include "rnnt_hat_impl.h"
+
+namespace rnnt {
+template rnntStatus_t run_hat<BF16>(const uint16_t*, uint16_t*, const float*, const int*, const int*, const int*, int, int,
+                                    float*, float*, void*, const rnntOptions&, int, bool);
+template rnntStatus_t run_hat<F16>(const uint16_t*, uint16_t*, const float*, const int*, const int*, const int*, int, int,
+                                   float*, float*, void*, const rnntOptions&, int, bool);
+}  // namespace rnnt
