@@ -7,11 +7,10 @@ tests/test_gpu_hat.py runs every case and checks that exactly the predicted kern
 A case: dtype, N, T, U (= maxU), A, blank; `off` = byte offset of the logits and gradients from a 16-byte boundary (the
 element-wise gradient form).  The blank sits at column 0, at A - 1 and at interior columns that are not the first lane of a
 16-byte packet."""
+from tests import forms_common as C
+from tests.forms_common import STORES, lattice_form, object_of          # noqa: F401  (this table's names)
 
 OBJECTS = {"f32": "rnnt_hat.hip", "f64": "rnnt_hat_f64.hip", "h16": "rnnt_hat_h16.hip"}
-# dtype -> (object, store tag, lattice type, element bytes)
-STORES = {"f32": ("f32", "rnnt::F32", "float", 4), "f64": ("f64", "rnnt::F64", "double", 8),
-          "bf16": ("h16", "rnnt::BF16", "float", 2), "f16": ("h16", "rnnt::F16", "float", 2)}
 STAGES = ("stats", "lattice", "coef", "grad")
 
 
@@ -27,34 +26,16 @@ def stats_group(row_bytes):
     return 4 if row_bytes <= 256 else 16 if row_bytes <= 4096 else 64
 
 
-def lat_stride(U):
-    return (U + 7) & ~7
-
-
 def predict(case, cus):
     """{stage: set of kernel names} the release rules launch for `case` on a device of `cus` compute units (a training
     call: both lattice directions)."""
     obj, tag, lat, esz = STORES[case["dtype"]]
     N, U = case["N"], case["U"]
-    up = lat_stride(U)
-    if up <= 64 and lat == "float" and 2 * N <= cus:
-        lattice = "rnnt::lattice_lin_kernel<0>"
-    elif up <= 64:
-        lattice = "rnnt::lattice_kernel<%s, 1, 1>" % lat
-    elif up <= 256:
-        lattice = "rnnt::lattice_kernel<%s, 8, 1>" % lat
-    elif up <= 512:
-        lattice = "rnnt::lattice_kernel<%s, 4, 2>" % lat
-    else:
-        lattice = "rnnt::lattice_kernel<%s, 8, 2>" % lat
+    lattice = lattice_form(lat, U, N, 2, cus)
     coef = "rnnt::coef_cell_kernel<%s>" % lat if U <= 48 else "rnnt::coef_kernel<%s, false>" % lat
     grad = "rnnt::hat_grad_kernel<%s>" % tag if case.get("off", 0) % 16 == 0 else "rnnt::hat_grad_elem_kernel<%s>" % tag
     return {"stats": {"rnnt::hat_stats_kernel<%s, %d>" % (tag, stats_group(case["A"] * esz))},
             "lattice": {lattice}, "coef": {coef}, "grad": {grad}}
-
-
-def object_of(case):
-    return STORES[case["dtype"]][0]
 
 
 def _case(name, dtype, N, T, U, A, blank, **kw):
@@ -83,17 +64,9 @@ UNREACHABLE = {}
 
 def predicted_rows(cus=256):
     """{(object, kernel): [cases]} the release rules reach with CASES on a device of `cus` compute units."""
-    rows = {}
-    for name, c in CASES.items():
-        for ks in predict(c, cus).values():
-            for k in ks:
-                rows.setdefault((object_of(c), k), []).append(name)
-    return rows
+    return C.predicted_rows(CASES, predict, cus)
 
 
 def expected_inventory(cus=256):
     """{object: set of kernels} the three code objects must hold exactly."""
-    inv = {o: set() for o in OBJECTS}
-    for (obj, k) in list(predicted_rows(cus)) + list(UNREACHABLE):
-        inv[obj].add(k)
-    return inv
+    return C.expected_inventory(OBJECTS, predicted_rows(cus), UNREACHABLE)

@@ -12,6 +12,8 @@
 import numpy as np
 import torch
 
+from tests.side_check import in_lattice_mask          # noqa: F401  (the rows the loss reads: t < T_b, u <= L_b)
+
 F = torch.nn.functional
 NEG = -1.0e30          # "log zero": -inf would turn logsumexp's derivative into NaN on nodes no path reaches
 
@@ -125,12 +127,3 @@ def hat_formula(logits, labels, act_lens, label_lens, blank=0):
         out[..., blank] = (cb + cl) * bsig - cb
         g[b, :T, :L + 1] = out
     return g
-
-
-def in_lattice_mask(shape, act_lens, label_lens):
-    """(N, T, U) bool: rows t < T_b, u <= L_b."""
-    N, T, U = shape[:3]
-    m = np.zeros((N, T, U), bool)
-    for b in range(N):
-        m[b, :int(act_lens[b]), :int(label_lens[b]) + 1] = True
-    return m

@@ -9,13 +9,12 @@ and the cases that reach them are joint_forms.py's, run through compute_rnnt_pru
 
 A loss case: dtype, N, T, U (= maxU), A, S, entry "loss"; `off` = byte offset of the logits and gradients from a 16-byte
 boundary (the element-wise gradient form).  A ranges case: the same with entry "ranges" (f, g instead of the logits)."""
+from tests import forms_common as C
 from tests import joint_forms as J
 from tests import kernel_forms as K
+from tests.forms_common import STORES, lattice_form, object_of          # noqa: F401  (this table's names)
 
 OBJECTS = {"f32": "rnnt_pruned.hip", "f64": "rnnt_pruned_f64.hip", "h16": "rnnt_pruned_h16.hip"}
-# dtype -> (object, store tag, lattice type, element bytes)
-STORES = {"f32": ("f32", "rnnt::F32", "float", 4), "f64": ("f64", "rnnt::F64", "double", 8),
-          "bf16": ("h16", "rnnt::BF16", "float", 2), "f16": ("h16", "rnnt::F16", "float", 2)}
 JOINT_OBJECT = {"joint_f32": "f32", "joint_bf16": "h16", "joint_f16": "h16"}
 STAGES = ("prep", "stats", "lattice", "coef", "grad", "partition", "window")
 COEF_CELL_MAX_U = 48
@@ -45,19 +44,6 @@ def stats_group(row_bytes):
     return 4 if row_bytes <= 256 else 16 if row_bytes <= 2048 else 64
 
 
-def lattice_form(lat, U, N, dirs, cus):
-    up = K.lat_stride(U)
-    if lat == "float" and up <= 64 and N * dirs <= cus:
-        return "rnnt::lattice_lin_kernel<0>"
-    if up <= 64:
-        return "rnnt::lattice_kernel<%s, 1, 1>" % lat
-    if up <= 256:
-        return "rnnt::lattice_kernel<%s, 8, 1>" % lat
-    if up <= 512:
-        return "rnnt::lattice_kernel<%s, 4, 2>" % lat
-    return "rnnt::lattice_kernel<%s, 8, 2>" % lat
-
-
 def predict(case, cus):
     """{stage: set of kernel names} the release rules launch for `case` on a device with `cus` compute units."""
     N, T, U, A = K.case_shape(case, cus)
@@ -77,10 +63,6 @@ def predict(case, cus):
     out["coef"] = {"rnnt::coef_kernel<%s, false>" % lat if U > COEF_CELL_MAX_U else "rnnt::coef_cell_kernel<%s>" % lat}
     out["grad"] = {"rnnt::pruned_grad_kernel<%s>" % tag if off % 16 == 0 else "rnnt::pruned_grad_elem_kernel<%s>" % tag}
     return out
-
-
-def object_of(case):
-    return STORES[case["dtype"]][0]
 
 
 def _case(name, dtype, N, T, U, A, S, entry="loss", **kw):
@@ -124,12 +106,7 @@ UNREACHABLE = {
 
 def predicted_rows(cus=256):
     """{(object, kernel): [cases]} the release rules reach with CASES on a device of `cus` compute units."""
-    rows = {}
-    for name, c in CASES.items():
-        for ks in predict(c, cus).values():
-            for k in ks:
-                rows.setdefault((object_of(c), k), []).append(name)
-    return rows
+    return C.predicted_rows(CASES, predict, cus)
 
 
 def joint_unreachable():
@@ -144,9 +121,4 @@ def joint_unreachable():
 
 def expected_inventory(cus=256):
     """{object: set of kernels} the three code objects must hold exactly."""
-    inv = {o: set() for o in OBJECTS}
-    for (obj, k) in predicted_rows(cus):
-        inv[obj].add(k)
-    for (obj, k) in list(UNREACHABLE) + list(joint_unreachable()):
-        inv[obj].add(k)
-    return inv
+    return C.expected_inventory(OBJECTS, predicted_rows(cus), list(UNREACHABLE) + list(joint_unreachable()))

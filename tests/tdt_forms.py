@@ -6,11 +6,10 @@ exactly the predicted kernels ran.
 
 A case: dtype, N, T, U (= maxU), A (token columns), durations; `off` = byte offset of the logits and gradients from a 16-byte
 boundary (the element-wise gradient form)."""
+from tests import forms_common as C
+from tests.forms_common import STORES, object_of                        # noqa: F401  (this table's names)
 
 OBJECTS = {"f32": "rnnt_tdt.hip", "f64": "rnnt_tdt_f64.hip", "h16": "rnnt_tdt_h16.hip"}
-# dtype -> (object, store tag, lattice type, element bytes)
-STORES = {"f32": ("f32", "rnnt::F32", "float", 4), "f64": ("f64", "rnnt::F64", "double", 8),
-          "bf16": ("h16", "rnnt::BF16", "float", 2), "f16": ("h16", "rnnt::F16", "float", 2)}
 STAGES = ("stats", "lattice", "coef", "grad")
 
 
@@ -35,10 +34,6 @@ def predict(case, cus):
             "grad": {"rnnt::tdt_grad_kernel<%s>" % tag if off % 16 == 0 else "rnnt::tdt_grad_elem_kernel<%s>" % tag}}
 
 
-def object_of(case):
-    return STORES[case["dtype"]][0]
-
-
 def _case(name, dtype, N, T, U, A, durations, **kw):
     return dict(name=name, dtype=dtype, N=N, T=T, U=U, A=A, durations=tuple(durations), **kw)
 
@@ -59,17 +54,9 @@ UNREACHABLE = {}
 
 def predicted_rows(cus=256):
     """{(object, kernel): [cases]} the release rules reach with CASES on a device of `cus` compute units."""
-    rows = {}
-    for name, c in CASES.items():
-        for ks in predict(c, cus).values():
-            for k in ks:
-                rows.setdefault((object_of(c), k), []).append(name)
-    return rows
+    return C.predicted_rows(CASES, predict, cus)
 
 
 def expected_inventory(cus=256):
     """{object: set of kernels} the three code objects must hold exactly."""
-    inv = {o: set() for o in OBJECTS}
-    for (obj, k) in list(predicted_rows(cus)) + list(UNREACHABLE):
-        inv[obj].add(k)
-    return inv
+    return C.expected_inventory(OBJECTS, predicted_rows(cus), UNREACHABLE)

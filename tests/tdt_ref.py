@@ -9,6 +9,8 @@
 import numpy as np
 import torch
 
+from tests.side_check import in_lattice_mask          # noqa: F401  (the rows the loss reads: t < T_b, u <= L_b)
+
 NEG = -1.0e30          # "log zero": -inf would turn logsumexp's derivative into NaN on nodes no path reaches
 
 
@@ -113,12 +115,3 @@ def _sample_brute(x, lab, T, L, A, durations, blank, sigma):
 def tdt_brute(logits, labels, act_lens, label_lens, durations, blank=0, sigma=0.0, weights=None):
     """tdt_autograd by enumeration of every path (tiny lattices)."""
     return _run(_sample_brute, logits, labels, act_lens, label_lens, durations, blank, sigma, weights)
-
-
-def in_lattice_mask(shape, act_lens, label_lens):
-    """(N, T, U) bool: rows t < T_b, u <= L_b."""
-    N, T, U = shape[:3]
-    m = np.zeros((N, T, U), bool)
-    for b in range(N):
-        m[b, :int(act_lens[b]), :int(label_lens[b]) + 1] = True
-    return m

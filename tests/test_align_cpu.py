@@ -7,52 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests.align_ref import path_score, viterbi_np
 from warprnnt_pytorch import _lib, rnnt_align
 
 
 # ----------------------------------------------------------------------------- numpy reference
-def viterbi_np(lp, labels, T, U, blank):
-    """lp: (maxT, maxU, A) log-probs of one sample (fp64); U = number of labels.  Returns (score, frames[U]).
-    Label predecessor (t, u-1) wins only when strictly better than the blank one (t-1, u)."""
-    lp = np.asarray(lp, dtype=np.float64)
-    if np.isnan(lp[:T, :U + 1, blank]).any() or (U and np.isnan(lp[np.arange(T)[:, None], np.arange(U)[None], labels[:U][None]]).any()):
-        return float("nan"), [-1] * U
-    v = np.full((T, U + 1), -np.inf)
-    v[0, 0] = 0.0
-    for t in range(T):
-        for u in range(U + 1):
-            if t == 0 and u == 0:
-                continue
-            stay = v[t - 1, u] + lp[t - 1, u, blank] if t > 0 else -np.inf
-            emit = v[t, u - 1] + lp[t, u - 1, labels[u - 1]] if u > 0 else -np.inf
-            v[t, u] = emit if emit > stay else stay
-    s = v[T - 1, U] + lp[T - 1, U, blank]
-    if not np.isfinite(s):
-        return s, [-1] * U
-    frames = [-1] * U
-    t, u = T - 1, U
-    while t > 0 or u > 0:
-        label = u > 0 and (t == 0 or v[t, u - 1] + lp[t, u - 1, labels[u - 1]] > v[t - 1, u] + lp[t - 1, u, blank])
-        if label:
-            frames[u - 1] = t
-            u -= 1
-        else:
-            t -= 1
-    return s, frames
-
-
-def path_score(lp, labels, T, U, blank, frames):
-    """log-probability of the path that emits label u at frames[u] (fp64)."""
-    lp = np.asarray(lp, dtype=np.float64)
-    s, u = 0.0, 0
-    for t in range(T):
-        while u < U and frames[u] == t:
-            s += lp[t, u, labels[u]]
-            u += 1
-        s += lp[t, u, blank]
-    return s
-
-
 def brute_force(lp, labels, T, U, blank):
     """Every path: every non-decreasing frame assignment of the U labels.  Best score, and the lexicographically
     smallest frames among the best (= the earliest emissions the tie rule asks for)."""

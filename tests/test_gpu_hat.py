@@ -15,52 +15,18 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests import gpu_support as G
 from tests import hat_forms as F
 from tests import hat_ref as R
-from tests.test_gpu_kernel_forms import _cus, _profiled
+from tests.gpu_support import (CODE, DEV, NAME, TORCH, assert_every_row_reached, assert_stages, call_forms, check, dev,
+                               options, place, profiled, ragged_lengths, stages_seen)
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-_TORCH = {"f32": torch.float32, "f64": torch.float64, "bf16": torch.bfloat16, "f16": torch.float16}
-_CODE = {"f32": 0, "f64": 1, "bf16": 2, "f16": 3}
-_NAME = {v: k for k, v in _TORCH.items()}
-_COST_TOL = {"f64": 1e-9, "f32": 1e-5, "bf16": 1e-5, "f16": 1e-5}
 
 
 def _hat():
     from warprnnt_pytorch import hat
     return hat
-
-
-def _opt(T, U, blank=0, stream=None):
-    from warprnnt_pytorch import _lib
-    s = stream if stream is not None else torch.cuda.current_stream()
-    return _lib.rnntOptions(loc=_lib.RNNT_GPU, num_threads=0, stream=s.cuda_stream, blank_label=blank, maxT=T, maxU=U,
-                            batch_first=True)
-
-
-def _lengths(N, T, U, rng):
-    tl = rng.integers(1, T + 1, size=N).astype(np.int32)
-    ll = rng.integers(0, U, size=N).astype(np.int32)
-    tl[0], ll[0] = T, U - 1
-    if N > 1:
-        tl[1] = 1
-    if N > 2:
-        ll[2] = 0
-    return tl, ll
-
-
-def _place(values, off, dtype):
-    """A device tensor of `values` `off` bytes past a 16-byte boundary inside a larger NaN buffer."""
-    esz = torch.finfo(dtype).bits // 8
-    n = values.numel()
-    buf = torch.full((n + 32 // esz,), float("nan"), dtype=dtype, device=DEV)
-    base = (-buf.data_ptr() % 16) // esz
-    v = buf[base + off // esz: base + off // esz + n].view(values.shape)
-    v.copy_(values)
-    assert v.data_ptr() % 16 == off
-    return v
 
 
 def _labels(rng, N, U, A, blank):
@@ -71,51 +37,29 @@ def _labels(rng, N, U, A, blank):
 
 def _problem(name, dtype, N, T, U, A, blank, rng=None, lengths=None, scale=2.0):
     rng = rng or np.random.default_rng(zlib.crc32(name.encode()))
-    tl, ll = lengths if lengths is not None else _lengths(N, T, U, rng)
+    tl, ll = lengths if lengths is not None else ragged_lengths(N, T, U, rng)
     labels = _labels(rng, N, U, A, blank)
-    x = torch.tensor(rng.standard_normal((N, T, U, A)) * scale, dtype=torch.float32).to(_TORCH[dtype])
+    x = torch.tensor(rng.standard_normal((N, T, U, A)) * scale, dtype=torch.float32).to(TORCH[dtype])
     mask = R.in_lattice_mask((N, T, U), tl, ll)
     x[torch.tensor(~mask)] = float("nan")
     return x, labels, tl, ll, mask
-
-
-def _dev(*arrs):
-    return [torch.tensor(np.ascontiguousarray(a), device=DEV) for a in arrs]
 
 
 def call(x, labels, tl, ll, blank=0, form="one", scale=None, grads=None, stream=None):
     """One C-ABI call form -> (status, costs, grads or None).  form: one | two | inplace | score | host."""
     h = _hat()
     N, T, U, A = x.shape
-    code = _CODE[_NAME[x.dtype]]
-    lab, ttl, tll = _dev(labels if labels.size else np.zeros((N, 1), np.int32), tl, ll)
-    cdt = torch.float64 if x.dtype == torch.float64 else torch.float32
-    costs = torch.full((N,), float("nan"), dtype=cdt, device=DEV)
-    ws = torch.empty(h.workspace_bytes(T, U, N, code), dtype=torch.uint8, device=DEV)
-    opt = _opt(T, U, blank, stream)
+    code = CODE[NAME[x.dtype]]
+    lab, ttl, tll = dev(labels if labels.size else np.zeros((N, 1), np.int32), tl, ll)
+    opt = options(T, U, blank, stream)
     lib = h.lib()
-    if grads is None and form not in ("score", "inplace", "host"):
-        grads = torch.full_like(x, float("nan"))
-    if form in ("one", "score", "inplace", "host"):
-        g = None if form == "score" else (x if form == "inplace" else grads)
-        gp = g.data_ptr() if g is not None else None
-        if form == "host":
-            hc = np.full(N, np.nan, dtype=np.float64 if cdt == torch.float64 else np.float32)
-            st = lib.compute_hat_loss(x.data_ptr(), gp, lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N,
-                                      hc.ctypes.data, ws.data_ptr(), opt, code)
-            return st, hc, (None if g is None else g.double().cpu().numpy())
-        st = lib.compute_hat_loss(x.data_ptr(), gp, lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N,
-                                  costs.data_ptr(), ws.data_ptr(), opt, code)
-        (stream or torch.cuda.current_stream()).synchronize()
-        return st, costs.cpu().numpy(), (None if g is None else g.double().cpu().numpy())
-    st = lib.compute_hat_loss_fwd(x.data_ptr(), lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N, costs.data_ptr(),
-                                  ws.data_ptr(), opt, code, 1)
-    assert st == 0
-    sc = None if scale is None else torch.tensor(scale, dtype=cdt, device=DEV)
-    st = lib.compute_hat_loss_bwd(x.data_ptr(), grads.data_ptr(), sc.data_ptr() if sc is not None else None, A, N,
-                                  ws.data_ptr(), opt, code)
-    torch.cuda.synchronize()
-    return st, costs.cpu().numpy(), grads.double().cpu().numpy()
+    lens = (lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N)
+    return call_forms(
+        x, form,
+        lambda gp, costs, ws: lib.compute_hat_loss(x.data_ptr(), gp, *lens, costs, ws, opt, code),
+        lambda costs, ws: lib.compute_hat_loss_fwd(x.data_ptr(), *lens, costs, ws, opt, code, 1),
+        lambda gp, sc, ws: lib.compute_hat_loss_bwd(x.data_ptr(), gp, sc, A, N, ws, opt, code),
+        h.workspace_bytes(T, U, N, code), scale, grads, stream)
 
 
 def _reference(x, labels, tl, ll, blank=0, weights=None, plain=False):
@@ -138,54 +82,30 @@ def _mag(ref, labels, ll, blank):
 
 
 def _check(dtype, got_c, got_g, ref_c, ref_g, mask, labels, ll, blank=0, scale=None, what=""):
-    w = np.ones(len(ref_c)) if scale is None else np.asarray(scale, np.float64)
-    tol = _COST_TOL[dtype]
-    print(what, "max |dcost| = %.3e" % np.abs(got_c - ref_c).max())
-    assert np.allclose(got_c, ref_c, rtol=tol, atol=tol), (what, got_c, ref_c)
-    if got_g is None:
-        return
-    assert not got_g[~mask].any(), (what, "padding must be exact zeros")
-    worst = 0.0
-    for b in range(len(ref_c)):
-        m = mask[b]
-        ref = ref_g[b:b + 1] * w[b]
-        mag = _mag(ref, labels[b:b + 1], ll[b:b + 1], blank)[0][m]
-        # (oracle.py: 16-bit storage on lattices of more than ~500 diagonals passes rel=1e-3 -- the fp32 lattice's own error)
-        rel = 1e-3 if dtype in ("bf16", "f16") and got_g.shape[1] + labels.shape[1] > 500 else None
-        r = O.grad_check(got_g[b][m], ref[0][m], mag, _TORCH[dtype], rel=rel)
-        worst = max(worst, r["max_err_over_quantum"])
-        assert r["passed"], ("%s sample %d" % (what, b), r)
-    print(what, "max gradient error / bound = %.3f" % worst)
+    """No sample of this loss is without a path while its logits are finite: a +inf reference cost is a fault."""
+    check(dtype, got_c, got_g, ref_c, ref_g, mask, lambda ref, b: _mag(ref, labels[b:b + 1], ll[b:b + 1], blank), scale, what,
+          infinite_ok=False, diagonals=mask.shape[1] + labels.shape[1])
 
 
 # ----------------------------------------------------------------------------- every form of tests/hat_forms.py
 @pytest.mark.parametrize("name", sorted(F.CASES))
 def test_hat_form(name):
     case = F.CASES[name]
-    cus = _cus()
+    cus = G.cus()
     N, T, U, A, blank, dtype = case["N"], case["T"], case["U"], case["A"], case["blank"], case["dtype"]
     x, labels, tl, ll, mask = _problem(name, dtype, N, T, U, A, blank)
     off = case.get("off", 0)
-    xv = _place(x.to(DEV), off, x.dtype)
-    gv = _place(torch.full_like(x, float("nan")).to(DEV), off, x.dtype)
-    (st, c, g), names = _profiled(lambda: call(xv, labels, tl, ll, blank, "one", grads=gv))
+    xv = place(x.to(DEV), off, x.dtype)
+    gv = place(torch.full_like(x, float("nan")).to(DEV), off, x.dtype)
+    (st, c, g), names = profiled(lambda: call(xv, labels, tl, ll, blank, "one", grads=gv))
     assert st == 0
-    want = F.predict(case, cus)
-    seen = {s: set() for s in F.STAGES}
-    for n in names:
-        s = F.stage_of(n)
-        if s is not None:
-            seen[s].add(n)
-    assert seen == want, (name, seen, want)
+    assert_stages(name, stages_seen(names, F.stage_of, F.STAGES), F.predict(case, cus))
     rc, rg = _reference(x, labels, tl, ll, blank)
     _check(dtype, c, g, rc, rg, mask, labels, ll, blank, what=name)
 
 
 def test_every_hat_row_reached_on_this_device():
-    rows = F.predicted_rows(_cus())
-    for obj, ks in F.expected_inventory().items():
-        for k in ks:
-            assert (obj, k) in rows or (obj, k) in F.UNREACHABLE, (obj, k)
+    assert_every_row_reached(F, G.cus())
 
 
 @pytest.mark.parametrize("dtype", ["f32", "f64", "bf16"])
@@ -272,7 +192,7 @@ def test_label_equal_to_blank_poisons_its_sample_only():
     _check("f32", c[keep], g[keep], rc, rg, mask[keep], labels[keep], ll[keep], blank, what="unpoisoned")
     from warprnnt_pytorch.hat import rnnt_loss_hat
     with pytest.raises(ValueError, match="blank"):
-        rnnt_loss_hat(torch.nan_to_num(x).to(DEV), *_dev(labels, tl, ll), blank=blank, reduction="none")
+        rnnt_loss_hat(torch.nan_to_num(x).to(DEV), *dev(labels, tl, ll), blank=blank, reduction="none")
 
 
 @pytest.mark.parametrize("dtype", ["f32", "f64", "bf16"])
@@ -341,11 +261,11 @@ def test_cross_check_against_rnntloss_of_hat_log_probs():
     from warprnnt_pytorch.hat import HATLoss, hat_log_probs
     N, T, U, A, blank = 4, 12, 8, 37, 9
     rng = np.random.default_rng(17)
-    tl, ll = _lengths(N, T, U, rng)
+    tl, ll = ragged_lengths(N, T, U, rng)
     tl[1] = 3
     labels = _labels(rng, N, U, A, blank)
     x = torch.tensor(rng.standard_normal((N, T, U, A)) * 2, dtype=torch.float64, device=DEV)
-    lab, ttl, tll = _dev(labels, tl, ll)
+    lab, ttl, tll = dev(labels, tl, ll)
     xa = x.clone().requires_grad_()
     la = HATLoss(blank=blank, reduction="none")(xa, lab, ttl, tll)
     la.sum().backward()
@@ -369,7 +289,7 @@ def test_autograd_reductions(reduction):
     x, labels, tl, ll, mask = _problem("ag", "f32", N, T, U, A, blank, rng=rng, lengths=(tl, ll))
     x = torch.nan_to_num(x)
     xd = x.to(DEV).requires_grad_()
-    loss = HATLoss(blank=blank, reduction=reduction)(xd, *_dev(labels, tl, ll))
+    loss = HATLoss(blank=blank, reduction=reduction)(xd, *dev(labels, tl, ll))
     go = torch.tensor([0.7, -1.3, 2.0][:loss.numel()], device=DEV).view(loss.shape)
     (loss * go).sum().backward()
     w = go.detach().cpu().numpy().reshape(-1)
@@ -387,7 +307,7 @@ def test_gradcheck_fp64():
     N, T, U, A, blank = 2, 4, 3, 5, 2
     rng = np.random.default_rng(2)
     labels = _labels(rng, N, U, A, blank)
-    lab, ttl, tll = _dev(labels, np.array([4, 3], np.int32), np.array([2, 1], np.int32))
+    lab, ttl, tll = dev(labels, np.array([4, 3], np.int32), np.array([2, 1], np.int32))
     x = torch.tensor(rng.standard_normal((N, T, U, A)), dtype=torch.float64, device=DEV, requires_grad=True)
     assert torch.autograd.gradcheck(lambda z: rnnt_loss_hat(z, lab, ttl, tll, blank, "none"), (x,), eps=1e-6, atol=1e-6,
                                     nondet_tol=1e-12)
@@ -408,7 +328,7 @@ def test_hip_graph_capture_and_replay():
     rng = np.random.default_rng(11)
     tl, ll = np.array([8, 6, 4], np.int32), np.array([4, 0, 2], np.int32)
     labels = _labels(rng, N, U, A, blank)
-    lab, ttl, tll = _dev(labels, tl, ll)
+    lab, ttl, tll = dev(labels, tl, ll)
     static_x = torch.zeros((N, T, U, A), device=DEV, requires_grad=True)
     h = _hat()
     h.lib()

@@ -4,7 +4,7 @@ _add_fwd_fastemit + _add_bwd, compute_rnnt_align_add, compute_rnnt_align) under 
 case's byte offsets from a 16-byte boundary, and the kernels recorded for each stage must be exactly the ones the release rules
 predict (joint_forms.predict_joint, with this device's compute-unit count).  Costs, df = sum_u dz and dg = sum_t dz are compared
 element by element with the fp64 oracle on the materialised joint z = f + g, at the bounds tests/test_gpu_add_network.py uses
-for the same dtype and shape class; alignments with the numpy Viterbi of tests/test_align_cpu.py.  Lengths are ragged (one
+for the same dtype and shape class; alignments with the numpy Viterbi of tests/align_ref.py.  Lengths are ragged (one
 sample at T_b = 1, one at U_b = 1), and the padded rows of f (t >= T_b) and g (u >= U_b) hold NaN, which must never be read
 (include/rnnt.h); the gradient buffers start as NaN and their padding must come back as exact zeros."""
 import zlib
@@ -13,40 +13,12 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gpu_support as G
 from tests import joint_forms as J
-from tests.test_align_cpu import path_score, viterbi_np
-from tests.test_gpu_kernel_forms import _cus, _profiled
+from tests.align_ref import path_score, viterbi_np
+from tests.gpu_support import DEV, TORCH, assert_stages, options, place, profiled, ragged_lengths, stages_seen
 
 pytestmark = pytest.mark.gpu
-
-_TORCH = {"f32": torch.float32, "f64": torch.float64, "bf16": torch.bfloat16, "f16": torch.float16}
-DEV = "cuda:0"
-
-
-def _lengths(N, T, U, rng):
-    tl = rng.integers(1, T + 1, size=N).astype(np.int32)
-    ll = rng.integers(0, U, size=N).astype(np.int32)
-    tl[0], ll[0] = T, U - 1                                          # one full sample: maxT / maxU are used
-    if N > 1:
-        tl[1] = 1                                                    # T_b = 1
-    if N > 2:
-        ll[2] = 0                                                    # U_b = 1
-    elif N == 2:
-        ll[1] = 0
-    return tl, ll
-
-
-def _view(values, off, dtype):
-    """A tensor of `values` placed `off` bytes past a 16-byte boundary, inside a larger NaN buffer."""
-    esz = torch.finfo(dtype).bits // 8
-    assert off % esz == 0
-    n = values.numel()
-    buf = torch.full((n + 32 // esz,), float("nan"), dtype=dtype, device=DEV)
-    base = (-buf.data_ptr() % 16) // esz                             # (torch allocations are 256-byte aligned: 0)
-    v = buf[base + off // esz: base + off // esz + n].view(values.shape)
-    v.copy_(values)
-    assert v.data_ptr() % 16 == off
-    return v
 
 
 def _problem(case, cus):
@@ -55,7 +27,7 @@ def _problem(case, cus):
     rng = np.random.default_rng(zlib.crc32(case["name"].encode()))
     f = rng.standard_normal((N, T, A)) * 1.5
     g = rng.standard_normal((N, U, A)) * 1.5
-    tl, ll = _lengths(N, T, U, rng)
+    tl, ll = ragged_lengths(N, T, U, rng, pair_without_labels=True)
     blank = 0
     labels = rng.integers(1, A, size=(N, U - 1)) if A > 1 else np.zeros((N, U - 1), np.int64)
     data = case.get("data")
@@ -95,21 +67,8 @@ def _scale(case, N):
     return (0.5 + 0.6 * (np.arange(N) % 5)).astype(np.float32) if case.get("scale") else None
 
 
-def _options(T, U, blank):
-    from warprnnt_pytorch import _lib
-    return _lib.rnntOptions(loc=_lib.RNNT_GPU, num_threads=0, stream=torch.cuda.current_stream().cuda_stream, blank_label=blank,
-                            maxT=T, maxU=U, batch_first=True)
-
-
 def _check_stages(case, names, cus):
-    want = J.predict_joint(case, cus)
-    seen = {s: set() for s in J.JSTAGES}
-    for n in names:
-        s = J.jstage_of(n)
-        if s is not None:
-            seen[s].add(n)
-    for s in J.JSTAGES:
-        assert seen[s] == want.get(s, set()), (case["name"], s, sorted(seen[s]), sorted(want.get(s, set())))
+    assert_stages(case["name"], stages_seen(names, J.jstage_of, J.JSTAGES), J.predict_joint(case, cus))
     return sorted({n for n in names if J.jstage_of(n)})
 
 
@@ -118,20 +77,20 @@ def run_loss_case(case, oracle, cus):
     from warprnnt_pytorch import _lib
     lib = _lib.lib()
     N, T, U, A = J.K.case_shape(case, cus)
-    dt = _TORCH[case["dtype"]]
+    dt = TORCH[case["dtype"]]
     f, g, labels, tl, ll, blank = _problem(case, cus)
     fs = torch.tensor(f, dtype=torch.float32).to(dt)                 # stored values: the oracle sees exactly these
     gs = torch.tensor(g, dtype=torch.float32).to(dt)
     off = dict({"f": 0, "g": 0, "df": 0, "dg": 0}, **case.get("off", {}))
-    tf = _view(_nan_padding(fs, tl, 1).to(DEV), off["f"], dt)
-    tg = _view(_nan_padding(gs, ll, 2).to(DEV), off["g"], dt)
-    df = _view(torch.full((N, T, A), float("nan"), dtype=dt), off["df"], dt)
-    dg = _view(torch.full((N, U, A), float("nan"), dtype=dt), off["dg"], dt)
+    tf = place(_nan_padding(fs, tl, 1).to(DEV), off["f"], dt)
+    tg = place(_nan_padding(gs, ll, 2).to(DEV), off["g"], dt)
+    df = place(torch.full((N, T, A), float("nan"), dtype=dt), off["df"], dt)
+    dg = place(torch.full((N, U, A), float("nan"), dtype=dt), off["dg"], dt)
     t_lab, t_tl, t_ll = (torch.tensor(v, device=DEV) for v in (labels, tl, ll))
     lab_ptr = t_lab.data_ptr() if t_lab.numel() else t_tl.data_ptr()
     costs = torch.full((N,), float("nan"), device=DEV)
     ws = torch.empty(_lib.workspace_bytes_add(T, U, N), dtype=torch.uint8, device=DEV)
-    opt = _options(T, U, blank)
+    opt = options(T, U, blank)
     sc = _scale(case, N)
     t_sc = torch.tensor(sc, device=DEV) if sc is not None else None
     sc_ptr = t_sc.data_ptr() if t_sc is not None else None
@@ -163,7 +122,7 @@ def run_loss_case(case, oracle, cus):
                                                   opt, code, 1, 0.0)
             return st or lib.compute_rnnt_loss_add_bwd_dt(*p, df.data_ptr(), dg.data_ptr(), sc_ptr, lab_ptr, t_ll.data_ptr(),
                                                           t_tl.data_ptr(), A, N, ws.data_ptr(), opt, code)
-    st, names = _profiled(call)
+    st, names = profiled(call)
     assert st == 0, (case["name"], st)
     reached = _check_stages(case, names, cus)
 
@@ -252,7 +211,7 @@ def run_align_case(case, cus):
     from warprnnt_pytorch import _lib
     lib = _lib.lib()
     N, T, U, A = J.K.case_shape(case, cus)
-    dt = _TORCH[case["dtype"]]
+    dt = TORCH[case["dtype"]]
     rng = np.random.default_rng(zlib.crc32(case["name"].encode()))
     planted = case.get("data") == "planted"
     blank = 0
@@ -260,12 +219,12 @@ def run_align_case(case, cus):
         acts, labels = _planted(N, T, U, A, rng)
         tl, ll = np.full(N, T, np.int32), np.full(N, U - 1, np.int32)
     else:
-        tl, ll = _lengths(N, T, U, rng)
+        tl, ll = ragged_lengths(N, T, U, rng, pair_without_labels=True)
         labels = rng.integers(1, A, size=(N, U - 1)).astype(np.int32)
     score = torch.full((N,), float("nan"), dtype=torch.float64, device=DEV)
     frames = torch.full((N, max(U - 1, 1)), -7, dtype=torch.int32, device=DEV)
     t_lab, t_tl, t_ll = (torch.tensor(v, device=DEV) for v in (labels, tl, ll))
-    opt = _options(T, U, blank)
+    opt = options(T, U, blank)
     code = {"f32": _lib.DT_F32, "f64": _lib.DT_F64, "bf16": _lib.DT_BF16, "f16": _lib.DT_F16}[case["dtype"]]
     if case["entry"] == "align_add":
         f = torch.tensor(rng.standard_normal((N, T, A)) * 1.5, dtype=torch.float32).to(dt)
@@ -288,7 +247,7 @@ def run_align_case(case, cus):
         call = lambda: lib.compute_rnnt_align(xd.data_ptr(), t_lab.data_ptr(), t_ll.data_ptr(), t_tl.data_ptr(), A, N,
                                               score.data_ptr(), frames.data_ptr(), ws.data_ptr(), opt, code)
         z = x.double().numpy()
-    st, names = _profiled(call)
+    st, names = profiled(call)
     assert st == 0, (case["name"], st)
     reached = _check_stages(case, names, cus)
     # no kernel of the additive joint's loss stages in an alignment call
@@ -318,7 +277,7 @@ _REACHED = {}
 @pytest.mark.parametrize("name", sorted(J.JCASES))
 def test_joint_form(oracle, name):
     case = J.JCASES[name]
-    cus = _cus()
+    cus = G.cus()
     if case["entry"] in ("align", "align_add"):
         _REACHED[name] = run_align_case(case, cus)
     else:

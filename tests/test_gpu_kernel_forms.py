@@ -4,64 +4,17 @@ exactly the one the release rules predict (kernel_forms.predict, with this devic
 every gradient element are then compared with the fp64 oracle at the per-dtype bounds of oracle.grad_bound, and the
 likelihoods kept in the workspace with the costs.  Lengths are ragged, one sample has T_b = 1 (U_b = 1 where the layout allows
 it), and the padding of padded-layout activations holds NaN, which must never be read."""
-import re
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 import torch
 
+from tests import gpu_support as G
 from tests import kernel_forms as K
+from tests.gpu_support import CALL, TORCH, assert_stages, profiled, stages_seen
 
 pytestmark = pytest.mark.gpu
-
-_TORCH = {"f32": torch.float32, "f64": torch.float64, "bf16": torch.bfloat16, "f16": torch.float16}
-_CALL = {"f32": "compute_rnnt_loss", "f64": "compute_rnnt_loss_fp64", "bf16": "compute_rnnt_loss_bf16", "f16": "compute_rnnt_loss_fp16"}
-
-
-def _cus():
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def _demangle(names):
-    mangled = [n for n in names if n.startswith("_Z")]
-    out = {n: n for n in names}
-    if mangled:
-        dem = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True).stdout.split("\n")
-        out.update(dict(zip(mangled, dem)))
-    return out
-
-
-def _normalise(name):
-    """'void rnnt::grad_flat_kernel<rnnt::F32, 1, 2, 1>(float const*, ...)' -> 'rnnt::grad_flat_kernel<rnnt::F32, 1, 2, 1>'"""
-    name = re.sub(r"^void ", "", name.strip())
-    depth = 0
-    for i, ch in enumerate(name):
-        if ch == "<":
-            depth += 1
-        elif ch == ">":
-            depth -= 1
-        elif ch == "(" and depth == 0:
-            return name[:i].strip()
-    return name
-
-
-def _kernels(prof):
-    """[normalised kernel name] of the device events a profiler recorded, in order."""
-    from torch.autograd import DeviceType
-    raw = [e.name for e in prof.events() if e.device_type == DeviceType.CUDA]
-    dem = _demangle(set(raw))
-    return [_normalise(dem[n]) for n in raw]
-
-
-def _profiled(fn):
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    return out, _kernels(prof)
 
 
 def test_profiler_records_kernel_names():
@@ -72,7 +25,7 @@ def test_profiler_records_kernel_names():
     lab = torch.ones(2, 2, dtype=torch.int32, device=dev)
     tl = torch.full((2,), 3, dtype=torch.int32, device=dev)
     ll = torch.full((2,), 2, dtype=torch.int32, device=dev)
-    _, names = _profiled(lambda: warp_rnnt.gpu_rnnt_async(x, lab, tl, ll, torch.zeros(2, device=dev), torch.zeros_like(x), 0))
+    _, names = profiled(lambda: warp_rnnt.gpu_rnnt_async(x, lab, tl, ll, torch.zeros(2, device=dev), torch.zeros_like(x), 0))
     assert any(K.stage_of(n) == "lattice" for n in names), names
 
 
@@ -80,7 +33,7 @@ def _inputs(case, cus, rng):
     N, T, U, A = K.case_shape(case, cus)
     d = case["dtype"]
     x64 = rng.standard_normal((N, T, U, A))
-    x = torch.tensor(x64, dtype=_TORCH[d])                          # stored values; the oracle sees exactly these
+    x = torch.tensor(x64, dtype=TORCH[d])                          # stored values; the oracle sees exactly these
     labels = rng.integers(1, A, size=(N, max(U - 1, 0))).astype(np.int32) if A > 1 else np.zeros((N, U - 1), np.int32)
     tl = rng.integers(1, T + 1, size=N).astype(np.int32)
     ll = rng.integers(0, U, size=N).astype(np.int32)
@@ -107,7 +60,7 @@ def run_case(case, oracle, cus):
     rng = np.random.default_rng(zlib.crc32(case["name"].encode()))
     N, T, U, A = K.case_shape(case, cus)
     x, labels, tl, ll, blank = _inputs(case, cus, rng)
-    dt = _TORCH[case["dtype"]]
+    dt = TORCH[case["dtype"]]
     code, esz = {torch.float32: (_lib.DT_F32, 4), torch.float64: (_lib.DT_F64, 8), torch.bfloat16: (_lib.DT_BF16, 2),
                  torch.float16: (_lib.DT_F16, 2)}[dt]
     cdt = torch.float64 if dt == torch.float64 else torch.float32
@@ -158,7 +111,7 @@ def run_case(case, oracle, cus):
             keep.append(host)
 
             def call():
-                st = getattr(lib, _CALL[case["dtype"]])(xd.data_ptr(), g.data_ptr(), t_lab.data_ptr(), t_ll.data_ptr(), t_tl.data_ptr(),
+                st = getattr(lib, CALL[case["dtype"]])(xd.data_ptr(), g.data_ptr(), t_lab.data_ptr(), t_ll.data_ptr(), t_tl.data_ptr(),
                                                          A, N, host.ctypes.data, ws.data_ptr(), opt)
                 costs.copy_(torch.from_numpy(host))
                 return st
@@ -175,7 +128,7 @@ def run_case(case, oracle, cus):
     if aux is not None:
         warp_rnnt.set_aux_stream(aux)
     try:
-        st, names = _profiled(call)
+        st, names = profiled(call)
     finally:
         if aux is not None:
             warp_rnnt.set_aux_stream(None)
@@ -183,13 +136,7 @@ def run_case(case, oracle, cus):
 
     # 1. the forms that ran
     want = K.predict(case, cus)
-    seen = {s: set() for s in K.STAGES}
-    for n in names:
-        s = K.stage_of(n)
-        if s is not None:
-            seen[s].add(n)
-    for s in K.STAGES:
-        assert seen[s] == want.get(s, set()), (case["name"], s, sorted(seen[s]), sorted(want.get(s, set())))
+    assert_stages(case["name"], stages_seen(names, K.stage_of, K.STAGES), want)
     ncoef = sum(1 for n in names if K.stage_of(n) == "coef")
     assert ncoef == K.coef_launches(case, cus) * (2 if case.get("aux") else 1) or not want.get("coef"), (case["name"], ncoef)
 
@@ -225,7 +172,7 @@ _REACHED = {}
 @pytest.mark.parametrize("name", sorted(K.CASES))
 def test_form(oracle, name):
     case = K.CASES[name]
-    cus = _cus()
+    cus = G.cus()
     names = run_case(case, oracle, cus)
     _REACHED[name] = sorted({n for n in names if K.stage_of(n)})
 

@@ -16,15 +16,15 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gpu_support as G
 from tests import joint_forms as J
 from tests import kernel_forms as K
 from tests import large_forms as L
-from tests.test_align_cpu import path_score, viterbi_np
-from tests.test_gpu_kernel_forms import _CALL, _TORCH, _cus, _profiled
+from tests.align_ref import path_score, viterbi_np
+from tests.gpu_support import CALL, DEV, TORCH, assert_stages, profiled, stages_seen
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 _INT = {torch.float32: torch.int32, torch.float64: torch.int64, torch.bfloat16: torch.int16, torch.float16: torch.int16}
 SLAB = 1 << 30                         # bytes of one device-side comparison slab
 
@@ -40,7 +40,7 @@ def _block(row):
     """Host block: stored activations (K, T, U, A) with NaN padding, labels, lengths, per-sample scales."""
     k, T, U, A = row["K"], row["T"], row["U"], row["A"]
     rng = np.random.default_rng(zlib.crc32(row["name"].encode()) + 1)
-    dt = _TORCH[row["dtype"]]
+    dt = TORCH[row["dtype"]]
     x = torch.tensor(rng.standard_normal((k, T, U, A)) * 1.5, dtype=torch.float32).to(dt)
     tl, ll = L.block_lengths(row)
     labels = rng.integers(1, A, size=(k, U - 1)).astype(np.int32)
@@ -98,13 +98,7 @@ def _rowsum_ratio(g, A, oracle, dt):
 
 def _stages(row, names, cus):
     want = L.predicted(row, cus)
-    seen = {}
-    for n in names:
-        s = K.stage_of(n) or J.jstage_of(n)
-        if s is not None:
-            seen.setdefault(s, set()).add(n)
-    for s in set(want) | set(seen):
-        assert seen.get(s, set()) == want.get(s, set()), (row["name"], s, sorted(seen.get(s, ())), sorted(want.get(s, ())))
+    assert_stages(row["name"], stages_seen(names, lambda n: K.stage_of(n) or J.jstage_of(n)), want)
     if want.get("coef"):    # the cell-per-thread kernel (maxU <= 48) runs in groups (launch_coef); the tiled one in one launch here
         ncoef = sum(1 for n in names if K.stage_of(n) == "coef")
         assert ncoef == (1 if row["U"] > 48 else K.coef_launches(L.case_of(row), cus)), (row["name"], ncoef)
@@ -113,7 +107,7 @@ def _stages(row, names, cus):
 def run_row(row, oracle, cus):
     from warprnnt_pytorch import _lib
     lib = _lib.lib()
-    dt = _TORCH[row["dtype"]]
+    dt = TORCH[row["dtype"]]
     code, esz = {torch.float32: (_lib.DT_F32, 4), torch.float64: (_lib.DT_F64, 8), torch.bfloat16: (_lib.DT_BF16, 2),
                  torch.float16: (_lib.DT_F16, 2)}[dt]
     cdt = torch.float64 if dt == torch.float64 else torch.float32
@@ -187,7 +181,7 @@ def run_row(row, oracle, cus):
         keep.append(host)
 
         def call():
-            st = getattr(lib, _CALL[row["dtype"]])(xp, gp, lab_ptr, t_ll.data_ptr(), t_tl.data_ptr(), A, N, host.ctypes.data,
+            st = getattr(lib, CALL[row["dtype"]])(xp, gp, lab_ptr, t_ll.data_ptr(), t_tl.data_ptr(), A, N, host.ctypes.data,
                                                    ws.data_ptr(), opt)
             costs.copy_(torch.from_numpy(host))
             return st
@@ -201,7 +195,7 @@ def run_row(row, oracle, cus):
             st = lib.compute_rnnt_loss_fwd(xp, lab_ptr, t_ll.data_ptr(), t_tl.data_ptr(), A, N, costs.data_ptr(), ws.data_ptr(), opt,
                                            code, 1)
             return st or lib.compute_rnnt_loss_bwd(xp, gp, sc_ptr, A, N, ws.data_ptr(), opt, code)
-    st, names = _profiled(call)
+    st, names = profiled(call)
     assert st == 0, (row["name"], st)
     _stages(row, names, cus)
     del ws
@@ -291,7 +285,7 @@ def _viterbi_check(row, z, labels, tl, ll, got_s, got_f, checked):
 def run_joint_row(row, oracle, cus):
     from warprnnt_pytorch import _lib
     lib = _lib.lib()
-    dt = _TORCH[row["dtype"]]
+    dt = TORCH[row["dtype"]]
     code = {"f32": _lib.DT_F32, "bf16": _lib.DT_BF16, "f16": _lib.DT_F16}[row["dtype"]]
     k, T, U, A, n = row["K"], row["T"], row["U"], row["A"], row["copies"]
     N = k * n
@@ -322,7 +316,7 @@ def run_joint_row(row, oracle, cus):
     if entry == "align_add":
         score = torch.full((N,), float("nan"), dtype=torch.float64, device=DEV)
         frames = torch.full((N, max(U - 1, 1)), -7, dtype=torch.int32, device=DEV)
-        st, names = _profiled(lambda: lib.compute_rnnt_align_add(*a, *lens, A, N, score.data_ptr(), frames.data_ptr(), ws.data_ptr(),
+        st, names = profiled(lambda: lib.compute_rnnt_align_add(*a, *lens, A, N, score.data_ptr(), frames.data_ptr(), ws.data_ptr(),
                                                                  opt, code))
         assert st == 0, (row["name"], st)
         _stages(row, names, cus)
@@ -350,7 +344,7 @@ def run_joint_row(row, oracle, cus):
         def call():
             st = lib.compute_rnnt_loss_add_fwd_dt(*a, *lens, A, N, costs.data_ptr(), ws.data_ptr(), opt, code, 1, 0.0)
             return st or lib.compute_rnnt_loss_add_bwd_dt(*a, *g2, sc_ptr, *lens, A, N, ws.data_ptr(), opt, code)
-    st, names = _profiled(call)
+    st, names = profiled(call)
     assert st == 0, (row["name"], st)
     _stages(row, names, cus)
     del ws
@@ -393,7 +387,7 @@ _REACHED = {}
 def test_large_form(oracle, name):
     row = L.ROWS[name]
     try:
-        names = (run_joint_row if row.get("joint") else run_row)(row, oracle, _cus())
+        names = (run_joint_row if row.get("joint") else run_row)(row, oracle, G.cus())
     finally:
         _free()
     _REACHED[name] = sorted({n for n in names if K.stage_of(n) or J.jstage_of(n)})
@@ -405,7 +399,7 @@ def test_every_large_kernel_reached_on_this_device():
     if len(_REACHED) < len(L.ROWS):
         pytest.skip("needs the whole table in this session")
     lines = []
-    for (obj, kernel), rows in sorted(L.covered(_cus()).items()):
+    for (obj, kernel), rows in sorted(L.covered(G.cus()).items()):
         assert any(kernel in _REACHED[r] for r in rows), (kernel, rows)
         lines.append("%-10s %-66s %s" % (obj, kernel, ", ".join(rows)))
     print("\n".join(lines))

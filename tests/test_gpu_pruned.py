@@ -6,7 +6,6 @@ of oracle.grad_bound; ragged lengths (one sample with T_b = 1, one with L_b = 0)
 gradient buffers that start as NaN (padding must come back as exact zeros).  Ranges cases are checked against the invariants of
 the rule.  Then the call forms, the reduction to compute_rnnt_loss_async, the impossible and invalid windows, the ranges
 against the numpy rule, and the recipe end to end."""
-import ctypes as C
 import zlib
 
 import numpy as np
@@ -14,38 +13,18 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests import gpu_support as G
 from tests import pruned_forms as P
 from tests import pruned_ref as R
-from tests.test_gpu_kernel_forms import _cus, _profiled
+from tests.gpu_support import (CODE, DEV, NAME, TORCH, assert_every_row_reached, assert_stages, call_forms, check, dev,
+                               options, place, profiled, ragged_lengths, stages_seen)
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-_TORCH = {"f32": torch.float32, "f64": torch.float64, "bf16": torch.bfloat16, "f16": torch.float16}
-_CODE = {"f32": 0, "f64": 1, "bf16": 2, "f16": 3}
 
 
 def _pl():
     from warprnnt_pytorch import pruned
     return pruned
-
-
-def _opt(T, U, blank=0, stream=None):
-    from warprnnt_pytorch import _lib
-    s = stream if stream is not None else torch.cuda.current_stream()
-    return _lib.rnntOptions(loc=_lib.RNNT_GPU, num_threads=0, stream=s.cuda_stream, blank_label=blank, maxT=T, maxU=U,
-                            batch_first=True)
-
-
-def _lengths(N, T, U, rng):
-    tl = rng.integers(1, T + 1, size=N).astype(np.int32)
-    ll = rng.integers(0, U, size=N).astype(np.int32)
-    tl[0], ll[0] = T, U - 1
-    if N > 1:
-        tl[1] = 1
-    if N > 2:
-        ll[2] = 0
-    return tl, ll
 
 
 def _windows(N, T, S, tl, ll, rng):
@@ -81,70 +60,32 @@ def _assert_real_lattice(c, tl, ll, ranges, S, what):
         assert any(np.isfinite(c[b]) and ll[b] > 0 for b in range(len(c))), (what, c, ll)
 
 
-def _place(values, off, dtype):
-    """A device tensor of `values` `off` bytes past a 16-byte boundary inside a larger NaN buffer."""
-    esz = torch.finfo(dtype).bits // 8
-    n = values.numel()
-    buf = torch.full((n + 32 // esz,), float("nan"), dtype=dtype, device=DEV)
-    base = (-buf.data_ptr() % 16) // esz
-    v = buf[base + off // esz: base + off // esz + n].view(values.shape)
-    v.copy_(values)
-    assert v.data_ptr() % 16 == off
-    return v
-
-
 def _problem(name, dtype, N, T, U, A, S, rng=None):
     rng = rng or np.random.default_rng(zlib.crc32(name.encode()))
-    tl, ll = _lengths(N, T, U, rng)
+    tl, ll = ragged_lengths(N, T, U, rng)
     labels = rng.integers(1, A, size=(N, U - 1)).astype(np.int32) if A > 1 else np.zeros((N, U - 1), np.int32)
     ranges = _windows(N, T, S, tl, ll, rng)
-    x = torch.tensor(rng.standard_normal((N, T, S, A)) * 2.0, dtype=torch.float32).to(_TORCH[dtype])
+    x = torch.tensor(rng.standard_normal((N, T, S, A)) * 2.0, dtype=torch.float32).to(TORCH[dtype])
     mask = R.in_lattice_mask((N, T, S), ranges, tl, ll)
     x[torch.tensor(~mask)] = float("nan")
     return x, labels, tl, ll, ranges, mask
 
 
-def _dev(*arrs):
-    return [torch.tensor(np.ascontiguousarray(a), device=DEV) for a in arrs]
-
-
 def call(x, labels, tl, ll, ranges, S, U, form="one", scale=None, grads=None, blank=0, stream=None):
     """One C-ABI call form -> (status, costs, grads or None).  form: one | two | inplace | score | host."""
     pl = _pl()
-    N, T = x.shape[0], x.shape[1]
-    A = x.shape[3]
-    code = _CODE[{torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16", torch.float16: "f16"}[x.dtype]]
-    lab, ttl, tll, tr = _dev(labels if labels.size else np.zeros((N, 1), np.int32), tl, ll, ranges)
-    cdt = torch.float64 if x.dtype == torch.float64 else torch.float32
-    costs = torch.full((N,), float("nan"), dtype=cdt, device=DEV)
-    ws = torch.empty(pl.workspace_bytes(T, U, N, code), dtype=torch.uint8, device=DEV)
-    opt = _opt(T, U, blank, stream)
+    N, T, A = x.shape[0], x.shape[1], x.shape[3]
+    code = CODE[NAME[x.dtype]]
+    lab, ttl, tll, tr = dev(labels if labels.size else np.zeros((N, 1), np.int32), tl, ll, ranges)
+    opt = options(T, U, blank, stream)
     lib = pl.lib()
-    if grads is None and form not in ("score", "inplace", "host"):
-        grads = torch.full_like(x, float("nan"))
-    if form in ("one", "score", "inplace", "host"):
-        g = None if form == "score" else (x if form == "inplace" else grads)
-        if form == "host":
-            hc = np.full(N, np.nan, dtype=np.float64 if cdt == torch.float64 else np.float32)
-            st = lib.compute_rnnt_loss_pruned(x.data_ptr(), g.data_ptr() if g is not None else None, tr.data_ptr(), S,
-                                              lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N, hc.ctypes.data,
-                                              ws.data_ptr(), opt, code)
-            return st, hc, None
-        st = lib.compute_rnnt_loss_pruned(x.data_ptr(), g.data_ptr() if g is not None else None, tr.data_ptr(), S,
-                                          lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N, costs.data_ptr(),
-                                          ws.data_ptr(), opt, code)
-        (stream or torch.cuda.current_stream()).synchronize()
-        return st, costs.cpu().numpy(), (None if g is None else g.float().cpu().numpy() if g.dtype != torch.float64
-                                         else g.cpu().numpy())
-    st = lib.compute_rnnt_loss_pruned_fwd(x.data_ptr(), tr.data_ptr(), S, lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A,
-                                          N, costs.data_ptr(), ws.data_ptr(), opt, code, 1)
-    assert st == 0
-    sc = None if scale is None else torch.tensor(scale, dtype=cdt, device=DEV)
-    st = lib.compute_rnnt_loss_pruned_bwd(x.data_ptr(), grads.data_ptr(), sc.data_ptr() if sc is not None else None, S, A, N,
-                                          ws.data_ptr(), opt, code)
-    torch.cuda.synchronize()
-    gg = grads.double().cpu().numpy()
-    return st, costs.cpu().numpy(), gg
+    lens = (lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N)
+    return call_forms(
+        x, form,
+        lambda gp, costs, ws: lib.compute_rnnt_loss_pruned(x.data_ptr(), gp, tr.data_ptr(), S, *lens, costs, ws, opt, code),
+        lambda costs, ws: lib.compute_rnnt_loss_pruned_fwd(x.data_ptr(), tr.data_ptr(), S, *lens, costs, ws, opt, code, 1),
+        lambda gp, sc, ws: lib.compute_rnnt_loss_pruned_bwd(x.data_ptr(), gp, sc, S, A, N, ws, opt, code),
+        pl.workspace_bytes(T, U, N, code), scale, grads, stream)
 
 
 def _reference(x, labels, tl, ll, ranges, weights=None):
@@ -169,36 +110,13 @@ def _mag(ref, labels, ranges, ll, blank=0):
 
 
 def _check(dtype, got_c, got_g, ref_c, ref_g, mask, labels, ranges, ll, scale=None, what=""):
-    w = np.ones(len(ref_c)) if scale is None else np.asarray(scale, np.float64)
-    fin = np.isfinite(ref_c)
-    assert np.array_equal(np.isposinf(got_c), np.isposinf(ref_c)), (what, got_c, ref_c)
-    tol = {"f64": 1e-9, "f32": 1e-5, "bf16": 1e-5, "f16": 1e-5}[dtype]
-    assert np.allclose(got_c[fin], ref_c[fin], rtol=tol, atol=tol), (what, got_c, ref_c)
-    if got_g is None:
-        return
-    assert not got_g[~mask].any(), (what, "padding must be exact zeros")
-    for b in range(len(ref_c)):
-        m = mask[b]
-        if not fin[b]:
-            assert np.isnan(got_g[b][m]).all(), (what, b, "impossible sample: NaN in-lattice gradients")
-            continue
-        ref = ref_g[b] * w[b] if scale is not None else ref_g[b]
-        ref = ref[m]
-        mag = _mag(ref_g[b:b + 1] * (w[b] if scale is not None else 1.0), labels[b:b + 1], ranges[b:b + 1], ll[b:b + 1])[0][m]
-        # (oracle.py: 16-bit storage on lattices of more than ~500 diagonals passes rel=1e-3 -- the fp32 lattice's own error)
-        rel = 1e-3 if dtype in ("bf16", "f16") and got_g.shape[1] + labels.shape[1] > 500 else None
-        O.assert_grads(got_g[b][m], ref, mag, _TORCH[dtype], rel=rel, what="%s sample %d" % (what, b))
+    check(dtype, got_c, got_g, ref_c, ref_g, mask,
+          lambda ref, b: _mag(ref, labels[b:b + 1], ranges[b:b + 1], ll[b:b + 1]), scale, what,
+          diagonals=mask.shape[1] + labels.shape[1])
 
 
 def _check_stages(case, names, cus):
-    want = P.predict(case, cus)
-    seen = {s: set() for s in P.STAGES}
-    for n in names:
-        s = P.stage_of(n)
-        if s is not None:
-            seen[s].add(n)
-    for s in P.STAGES:
-        assert seen[s] == want[s], (case["name"], s, sorted(seen[s]), sorted(want[s]))
+    assert_stages(case["name"], stages_seen(names, P.stage_of, P.STAGES), P.predict(case, cus))
 
 
 # ----------------------------------------------------------------------------- every form of tests/pruned_forms.py
@@ -206,9 +124,9 @@ def _run_loss_case(case, cus):
     N, T, U, A = P.K.case_shape(case, cus)
     S, dtype = case["S"], case["dtype"]
     x, labels, tl, ll, ranges, mask = _problem(case["name"], dtype, N, T, U, A, S)
-    xv = _place(x.to(DEV), case.get("off", 0), x.dtype)
-    gv = _place(torch.full_like(x, float("nan")).to(DEV), case.get("off", 0), x.dtype)
-    (st, c, g), names = _profiled(lambda: call(xv, labels, tl, ll, ranges, S, U, "one", grads=gv))
+    xv = place(x.to(DEV), case.get("off", 0), x.dtype)
+    gv = place(torch.full_like(x, float("nan")).to(DEV), case.get("off", 0), x.dtype)
+    (st, c, g), names = profiled(lambda: call(xv, labels, tl, ll, ranges, S, U, "one", grads=gv))
     assert st == 0
     _check_stages(case, names, cus)
     assert not any(n.startswith(("rnnt::row_stats", "rnnt::grad_flat_kernel", "rnnt::grad_rows_kernel")) for n in names)
@@ -221,24 +139,24 @@ def _run_ranges_case(case, cus):
     N, T, U, A = P.K.case_shape(case, cus)
     dtype, S = case["dtype"], case["S"]
     rng = np.random.default_rng(zlib.crc32(case["name"].encode()))
-    tl, ll = _lengths(N, T, U, rng)
-    f = torch.tensor(rng.standard_normal((N, T, A)), dtype=torch.float32).to(_TORCH[dtype])
-    g = torch.tensor(rng.standard_normal((N, U, A)), dtype=torch.float32).to(_TORCH[dtype])
+    tl, ll = ragged_lengths(N, T, U, rng)
+    f = torch.tensor(rng.standard_normal((N, T, A)), dtype=torch.float32).to(TORCH[dtype])
+    g = torch.tensor(rng.standard_normal((N, U, A)), dtype=torch.float32).to(TORCH[dtype])
     off = case.get("off", {})
-    fv, gv = _place(f.to(DEV), off.get("f", 0), f.dtype), _place(g.to(DEV), off.get("g", 0), g.dtype)
+    fv, gv = place(f.to(DEV), off.get("f", 0), f.dtype), place(g.to(DEV), off.get("g", 0), g.dtype)
     labels = rng.integers(1, A, size=(N, U - 1)).astype(np.int32) if A > 1 else np.zeros((N, U - 1), np.int32)
-    lab, ttl, tll = _dev(labels, tl, ll)
+    lab, ttl, tll = dev(labels, tl, ll)
     pl = _pl()
     out = torch.full((N, T), -7, dtype=torch.int32, device=DEV)
-    ws = torch.empty(pl.workspace_bytes(T, U, N, _CODE[dtype]), dtype=torch.uint8, device=DEV)
+    ws = torch.empty(pl.workspace_bytes(T, U, N, CODE[dtype]), dtype=torch.uint8, device=DEV)
 
     def run():
         st = pl.lib().compute_rnnt_prune_ranges_add(fv.data_ptr(), gv.data_ptr(), lab.data_ptr(), tll.data_ptr(),
-                                                    ttl.data_ptr(), A, N, S, out.data_ptr(), ws.data_ptr(), _opt(T, U),
-                                                    _CODE[dtype])
+                                                    ttl.data_ptr(), A, N, S, out.data_ptr(), ws.data_ptr(), options(T, U),
+                                                    CODE[dtype])
         torch.cuda.synchronize()
         return st
-    st, names = _profiled(run)
+    st, names = profiled(run)
     assert st == 0
     _check_stages(case, names, cus)
     r = out.cpu().numpy()
@@ -252,7 +170,7 @@ def _run_ranges_case(case, cus):
 @pytest.mark.parametrize("name", sorted(P.CASES))
 def test_pruned_form(name):
     case = P.CASES[name]
-    cus = _cus()
+    cus = G.cus()
     if case["entry"] == "ranges":
         _run_ranges_case(case, cus)
     else:
@@ -260,12 +178,7 @@ def test_pruned_form(name):
 
 
 def test_every_pruned_row_reached_on_this_device():
-    """Every kernel of the built code objects (the table at its default of 256 compute units: tests/test_pruned_cpu.py checks it
-    against the objects) is reached by some case on THIS device's compute-unit count, or is listed as unreachable."""
-    rows = P.predicted_rows(_cus())
-    for obj, ks in P.expected_inventory().items():
-        for k in ks:
-            assert (obj, k) in rows or (obj, k) in P.UNREACHABLE or (obj, k) in P.joint_unreachable(), (obj, k)
+    assert_every_row_reached(P, G.cus(), P.joint_unreachable())
 
 
 # ----------------------------------------------------------------------------- call forms, equivalences, edge cases
@@ -312,26 +225,26 @@ def test_full_windows_equal_the_materialised_loss(dtype):
     from warprnnt_pytorch import _lib
     N, T, U, A = 4, 8, 6, 37
     rng = np.random.default_rng(11)
-    tl, ll = _lengths(N, T, U, rng)
+    tl, ll = ragged_lengths(N, T, U, rng)
     labels = rng.integers(1, A, size=(N, U - 1)).astype(np.int32)
-    x = torch.tensor(rng.standard_normal((N, T, U, A)), dtype=torch.float32).to(_TORCH[dtype]).to(DEV)
+    x = torch.tensor(rng.standard_normal((N, T, U, A)), dtype=torch.float32).to(TORCH[dtype]).to(DEV)
     ranges = np.zeros((N, T), np.int32)
     st, c, g = call(x, labels, tl, ll, ranges, U, U, "one")
     assert st == 0
-    lab, ttl, tll = _dev(labels, tl, ll)
+    lab, ttl, tll = dev(labels, tl, ll)
     cdt = torch.float64 if dtype == "f64" else torch.float32
     c0 = torch.empty(N, dtype=cdt, device=DEV)
     g0 = torch.empty_like(x)
     ws = torch.empty(_lib.workspace_bytes(T, U, N, True, 8 if dtype == "f64" else 4), dtype=torch.uint8, device=DEV)
     st = _lib.lib().compute_rnnt_loss_async(x.data_ptr(), g0.data_ptr(), lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A,
-                                            N, c0.data_ptr(), None, ws.data_ptr(), _opt(T, U), _CODE[dtype])
+                                            N, c0.data_ptr(), None, ws.data_ptr(), options(T, U), CODE[dtype])
     torch.cuda.synchronize()
     assert st == 0
     c0, g0 = c0.cpu().numpy(), g0.double().cpu().numpy()
     tol = 1e-9 if dtype == "f64" else 1e-5
     assert np.allclose(c, c0, rtol=tol, atol=tol)
     mag = np.abs(g0) + np.abs(g0).sum(-1, keepdims=True)
-    O.assert_grads(g, g0, mag, _TORCH[dtype], what="S = maxU")
+    O.assert_grads(g, g0, mag, TORCH[dtype], what="S = maxU")
 
 
 def test_no_path_and_invalid_start():
@@ -385,7 +298,7 @@ def test_no_materialised_kernels_and_no_full_tensor():
     labels = torch.tensor(rng.integers(1, A, size=(N, U - 1)), dtype=torch.int32, device=DEV)
     f = torch.randn(N, T, A, device=DEV)
     g = torch.randn(N, U, A, device=DEV)
-    ttl, tll = _dev(tl, ll)
+    ttl, tll = dev(tl, ll)
     ranges = pl.prune_ranges(f, g, labels, ttl, tll, S)
     logits = (f[:, :, None, :] + pl.prune_inputs(f, g, ranges, S)[1]).contiguous().requires_grad_(True)
     torch.cuda.synchronize()
@@ -396,7 +309,7 @@ def test_no_materialised_kernels_and_no_full_tensor():
         loss = pl.rnnt_loss_pruned(logits, labels, ttl, tll, ranges)
         loss.backward()
         return loss
-    _, names = _profiled(run)
+    _, names = profiled(run)
     peak = torch.cuda.max_memory_allocated() - base
     assert any(n.startswith("rnnt::pruned_stats_kernel") for n in names), names
     assert any(n.startswith("rnnt::pruned_grad_kernel") for n in names), names
@@ -424,15 +337,15 @@ def test_prune_ranges_against_the_rule(dtype):
     pl = _pl()
     rng = np.random.default_rng(21)
     N, T, U, A, S = 6, 24, 11, 40, 4
-    tl, ll = _lengths(N, T, U, rng)
+    tl, ll = ragged_lengths(N, T, U, rng)
     tl[:] = np.maximum(tl, 4)
     # random inputs: invariants, and the occupancy the windows capture against the reference's
     f = rng.standard_normal((N, T, A))
     g = rng.standard_normal((N, U, A))
     labels = rng.integers(1, A, size=(N, U - 1)).astype(np.int32)
-    tf = torch.tensor(f, dtype=torch.float32).to(_TORCH[dtype]).to(DEV)
-    tg = torch.tensor(g, dtype=torch.float32).to(_TORCH[dtype]).to(DEV)
-    lab, ttl, tll = _dev(labels, tl, ll)
+    tf = torch.tensor(f, dtype=torch.float32).to(TORCH[dtype]).to(DEV)
+    tg = torch.tensor(g, dtype=torch.float32).to(TORCH[dtype]).to(DEV)
+    lab, ttl, tll = dev(labels, tl, ll)
     r = pl.prune_ranges(tf, tg, lab, ttl, tll, S).cpu().numpy()
     for b in range(N):
         Tb, L = int(tl[b]), int(ll[b])
@@ -448,12 +361,12 @@ def test_prune_ranges_against_the_rule(dtype):
         assert abs(got_mass - ref_mass) <= 1e-4 * ref_mass, (b, got_mass, ref_mass)
     # planted, peaked inputs: exactly the numpy rule
     f, g, labels = _planted(N, T, U, A, rng)
-    tf = torch.tensor(f, dtype=torch.float32).to(_TORCH[dtype]).to(DEV)
-    tg = torch.tensor(g, dtype=torch.float32).to(_TORCH[dtype]).to(DEV)
+    tf = torch.tensor(f, dtype=torch.float32).to(TORCH[dtype]).to(DEV)
+    tg = torch.tensor(g, dtype=torch.float32).to(TORCH[dtype]).to(DEV)
     lab = torch.tensor(labels, device=DEV)
     tl[:] = T
     ll[:] = U - 1
-    ttl, tll = _dev(tl, ll)
+    ttl, tll = dev(tl, ll)
     r = pl.prune_ranges(tf, tg, lab, ttl, tll, S).cpu().numpy()
     for b in range(N):
         gam = R.occupancy_add(tf[b].double().cpu().numpy(), tg[b].double().cpu().numpy(), labels[b], T, U - 1)
@@ -461,7 +374,7 @@ def test_prune_ranges_against_the_rule(dtype):
     # infeasible samples: L_b > T_b (S - 1)
     tl2 = np.array([2, 3, T, T, T, T], np.int32)
     ll2 = np.array([U - 1, U - 1, 2, 0, 5, U - 1], np.int32)
-    ttl, tll = _dev(tl2, ll2)
+    ttl, tll = dev(tl2, ll2)
     r = pl.prune_ranges(tf, tg, lab, ttl, tll, S).cpu().numpy()
     for b in (0, 1):
         Tb, L = int(tl2[b]), int(ll2[b])
@@ -493,7 +406,7 @@ def test_recipe_against_the_additive_joint():
     tl = np.full(N, T, np.int32)
     ll = np.full(N, U - 1, np.int32)
     tf, tg = torch.tensor(f, dtype=torch.float32, device=DEV), torch.tensor(g, dtype=torch.float32, device=DEV)
-    lab, ttl, tll = _dev(labels, tl, ll)
+    lab, ttl, tll = dev(labels, tl, ll)
     simple = RNNTLossAdd(reduction="none")(tf, tg, lab, ttl, tll)
     for S, tol in ((U, 1e-5), (4, 1e-3)):
         r = pl.prune_ranges(tf, tg, lab, ttl, tll, S)
@@ -529,7 +442,7 @@ def test_backprop_through_a_joiner():
         return j2(torch.tanh(j1(a + l)))
     am, lm = am0.to(DEV).requires_grad_(True), lm0.to(DEV).requires_grad_(True)
     j1.to(DEV), j2.to(DEV)
-    lab, ttl, tll, tr = _dev(labels, tl, ll, ranges)
+    lab, ttl, tll, tr = dev(labels, tl, ll, ranges)
     a_p, l_p = pl.prune_inputs(am, lm, tr, S)
     loss = pl.RNNTLossPruned(reduction="sum")(joiner(a_p, l_p).contiguous(), lab, ttl, tll, tr)
     loss.backward()
@@ -559,9 +472,9 @@ def test_autograd_reductions_and_grad_output(dtype):
     for b in range(N):
         ranges[b, :tl[b]] = R.ranges_rule(rng.random((tl[b], ll[b] + 1)), int(tl[b]), int(ll[b]), S)
     mask = R.in_lattice_mask((N, T, S), ranges, tl, ll)
-    x0 = torch.tensor(rng.standard_normal((N, T, S, A)), dtype=_TORCH[dtype])
+    x0 = torch.tensor(rng.standard_normal((N, T, S, A)), dtype=TORCH[dtype])
     x0[torch.tensor(~mask)] = float("nan")
-    lab, ttl, tll, tr = _dev(labels, tl, ll, ranges)
+    lab, ttl, tll, tr = dev(labels, tl, ll, ranges)
     w = np.array([0.5, 2.0, -1.0, 1.5])
     ref_c, ref_g = _reference(x0, labels, tl, ll, ranges)
     _, ref_gw = _reference(x0, labels, tl, ll, ranges, weights=w)
@@ -599,7 +512,7 @@ def test_autograd_without_labels():
     x0[torch.tensor(~mask)] = float("nan")
     ref_c, ref_g = _reference(x0, labels, tl, ll, ranges)
     x = x0.to(DEV).requires_grad_(True)
-    ttl, tll, tr = _dev(tl, ll, ranges)
+    ttl, tll, tr = dev(tl, ll, ranges)
     lab = torch.zeros((N, 0), dtype=torch.int32, device=DEV)
     loss = pl.rnnt_loss_pruned(x, lab, ttl, tll, tr, reduction="none")
     loss.sum().backward()

@@ -13,16 +13,13 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests import gpu_support as G
 from tests import tdt_forms as F
 from tests import tdt_ref as R
-from tests.test_gpu_kernel_forms import _cus, _profiled
+from tests.gpu_support import (CODE, DEV, NAME, TORCH, assert_every_row_reached, assert_stages, call_forms, check, dev,
+                               options, place, profiled, ragged_lengths, stages_seen)
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-_TORCH = {"f32": torch.float32, "f64": torch.float64, "bf16": torch.bfloat16, "f16": torch.float16}
-_CODE = {"f32": 0, "f64": 1, "bf16": 2, "f16": 3}
-_NAME = {v: k for k, v in _TORCH.items()}
 
 
 def _tdt():
@@ -30,48 +27,14 @@ def _tdt():
     return tdt
 
 
-def _opt(T, U, blank=0, stream=None):
-    from warprnnt_pytorch import _lib
-    s = stream if stream is not None else torch.cuda.current_stream()
-    return _lib.rnntOptions(loc=_lib.RNNT_GPU, num_threads=0, stream=s.cuda_stream, blank_label=blank, maxT=T, maxU=U,
-                            batch_first=True)
-
-
-def _lengths(N, T, U, rng):
-    tl = rng.integers(1, T + 1, size=N).astype(np.int32)
-    ll = rng.integers(0, U, size=N).astype(np.int32)
-    tl[0], ll[0] = T, U - 1
-    if N > 1:
-        tl[1] = 1
-    if N > 2:
-        ll[2] = 0
-    return tl, ll
-
-
-def _place(values, off, dtype):
-    """A device tensor of `values` `off` bytes past a 16-byte boundary inside a larger NaN buffer."""
-    esz = torch.finfo(dtype).bits // 8
-    n = values.numel()
-    buf = torch.full((n + 32 // esz,), float("nan"), dtype=dtype, device=DEV)
-    base = (-buf.data_ptr() % 16) // esz
-    v = buf[base + off // esz: base + off // esz + n].view(values.shape)
-    v.copy_(values)
-    assert v.data_ptr() % 16 == off
-    return v
-
-
 def _problem(name, dtype, N, T, U, A, durations, rng=None, lengths=None, scale=2.0):
     rng = rng or np.random.default_rng(zlib.crc32(name.encode()))
-    tl, ll = lengths if lengths is not None else _lengths(N, T, U, rng)
+    tl, ll = lengths if lengths is not None else ragged_lengths(N, T, U, rng)
     labels = rng.integers(0, A, size=(N, U - 1)).astype(np.int32)
-    x = torch.tensor(rng.standard_normal((N, T, U, A + len(durations))) * scale, dtype=torch.float32).to(_TORCH[dtype])
+    x = torch.tensor(rng.standard_normal((N, T, U, A + len(durations))) * scale, dtype=torch.float32).to(TORCH[dtype])
     mask = R.in_lattice_mask((N, T, U), tl, ll)
     x[torch.tensor(~mask)] = float("nan")
     return x, labels, tl, ll, mask
-
-
-def _dev(*arrs):
-    return [torch.tensor(np.ascontiguousarray(a), device=DEV) for a in arrs]
 
 
 def call(x, labels, tl, ll, durations, form="one", scale=None, grads=None, blank=0, sigma=0.0, stream=None):
@@ -80,36 +43,18 @@ def call(x, labels, tl, ll, durations, form="one", scale=None, grads=None, blank
     N, T, U, W = x.shape
     D = len(durations)
     A = W - D
-    code = _CODE[_NAME[x.dtype]]
-    lab, ttl, tll = _dev(labels if labels.size else np.zeros((N, 1), np.int32), tl, ll)
-    cdt = torch.float64 if x.dtype == torch.float64 else torch.float32
-    costs = torch.full((N,), float("nan"), dtype=cdt, device=DEV)
-    ws = torch.empty(t.workspace_bytes(T, U, N, D, code), dtype=torch.uint8, device=DEV)
+    code = CODE[NAME[x.dtype]]
+    lab, ttl, tll = dev(labels if labels.size else np.zeros((N, 1), np.int32), tl, ll)
     dur = (C.c_int * D)(*durations)
-    opt = _opt(T, U, blank, stream)
+    opt = options(T, U, blank, stream)
     lib = t.lib()
-    if grads is None and form not in ("score", "inplace", "host"):
-        grads = torch.full_like(x, float("nan"))
-    if form in ("one", "score", "inplace", "host"):
-        g = None if form == "score" else (x if form == "inplace" else grads)
-        gp = g.data_ptr() if g is not None else None
-        if form == "host":
-            hc = np.full(N, np.nan, dtype=np.float64 if cdt == torch.float64 else np.float32)
-            st = lib.compute_tdt_loss(x.data_ptr(), gp, dur, D, sigma, lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N,
-                                      hc.ctypes.data, ws.data_ptr(), opt, code)
-            return st, hc, (None if g is None else g.double().cpu().numpy())
-        st = lib.compute_tdt_loss(x.data_ptr(), gp, dur, D, sigma, lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N,
-                                  costs.data_ptr(), ws.data_ptr(), opt, code)
-        (stream or torch.cuda.current_stream()).synchronize()
-        return st, costs.cpu().numpy(), (None if g is None else g.double().cpu().numpy())
-    st = lib.compute_tdt_loss_fwd(x.data_ptr(), dur, D, sigma, lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N,
-                                  costs.data_ptr(), ws.data_ptr(), opt, code, 1)
-    assert st == 0
-    sc = None if scale is None else torch.tensor(scale, dtype=cdt, device=DEV)
-    st = lib.compute_tdt_loss_bwd(x.data_ptr(), grads.data_ptr(), sc.data_ptr() if sc is not None else None, dur, D, A, N,
-                                  ws.data_ptr(), opt, code)
-    torch.cuda.synchronize()
-    return st, costs.cpu().numpy(), grads.double().cpu().numpy()
+    lens = (lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(), A, N)
+    return call_forms(
+        x, form,
+        lambda gp, costs, ws: lib.compute_tdt_loss(x.data_ptr(), gp, dur, D, sigma, *lens, costs, ws, opt, code),
+        lambda costs, ws: lib.compute_tdt_loss_fwd(x.data_ptr(), dur, D, sigma, *lens, costs, ws, opt, code, 1),
+        lambda gp, sc, ws: lib.compute_tdt_loss_bwd(x.data_ptr(), gp, sc, dur, D, A, N, ws, opt, code),
+        t.workspace_bytes(T, U, N, D, code), scale, grads, stream)
 
 
 def _reference(x, labels, tl, ll, durations, blank=0, sigma=0.0, weights=None):
@@ -133,24 +78,8 @@ def _mag(ref, labels, ll, A, blank):
 
 
 def _check(dtype, got_c, got_g, ref_c, ref_g, mask, labels, ll, A, blank=0, scale=None, what=""):
-    w = np.ones(len(ref_c)) if scale is None else np.asarray(scale, np.float64)
-    fin = np.isfinite(ref_c)
-    assert np.array_equal(np.isposinf(got_c), np.isposinf(ref_c)), (what, got_c, ref_c)
-    tol = {"f64": 1e-9, "f32": 1e-5, "bf16": 1e-5, "f16": 1e-5}[dtype]
-    assert np.allclose(got_c[fin], ref_c[fin], rtol=tol, atol=tol), (what, got_c, ref_c)
-    if got_g is None:
-        return
-    assert not got_g[~mask].any(), (what, "padding must be exact zeros")
-    for b in range(len(ref_c)):
-        m = mask[b]
-        if not fin[b]:
-            assert np.isnan(got_g[b][m]).all(), (what, b, "no path: NaN in-lattice gradients")
-            continue
-        ref = ref_g[b:b + 1] * w[b]
-        mag = _mag(ref, labels[b:b + 1], ll[b:b + 1], A, blank)[0][m]
-        # (oracle.py: 16-bit storage on lattices of more than ~500 diagonals passes rel=1e-3 -- the fp32 lattice's own error)
-        rel = 1e-3 if dtype in ("bf16", "f16") and got_g.shape[1] + labels.shape[1] > 500 else None
-        O.assert_grads(got_g[b][m], ref[0][m], mag, _TORCH[dtype], rel=rel, what="%s sample %d" % (what, b))
+    check(dtype, got_c, got_g, ref_c, ref_g, mask, lambda ref, b: _mag(ref, labels[b:b + 1], ll[b:b + 1], A, blank), scale, what,
+          diagonals=mask.shape[1] + labels.shape[1])
 
 
 def _assert_real(c, ll, what):
@@ -162,31 +91,22 @@ def _assert_real(c, ll, what):
 @pytest.mark.parametrize("name", sorted(F.CASES))
 def test_tdt_form(name):
     case = F.CASES[name]
-    cus = _cus()
+    cus = G.cus()
     N, T, U, A, durs, dtype = case["N"], case["T"], case["U"], case["A"], case["durations"], case["dtype"]
     x, labels, tl, ll, mask = _problem(name, dtype, N, T, U, A, durs)
     off = case.get("off", 0)
-    xv = _place(x.to(DEV), off, x.dtype)
-    gv = _place(torch.full_like(x, float("nan")).to(DEV), off, x.dtype)
-    (st, c, g), names = _profiled(lambda: call(xv, labels, tl, ll, durs, "one", grads=gv))
+    xv = place(x.to(DEV), off, x.dtype)
+    gv = place(torch.full_like(x, float("nan")).to(DEV), off, x.dtype)
+    (st, c, g), names = profiled(lambda: call(xv, labels, tl, ll, durs, "one", grads=gv))
     assert st == 0
-    want = F.predict(case, cus)
-    seen = {s: set() for s in F.STAGES}
-    for n in names:
-        s = F.stage_of(n)
-        if s is not None:
-            seen[s].add(n)
-    assert seen == want, (name, seen, want)
+    assert_stages(name, stages_seen(names, F.stage_of, F.STAGES), F.predict(case, cus))
     rc, rg = _reference(x, labels, tl, ll, durs)
     _assert_real(c, ll, name)
     _check(dtype, c, g, rc, rg, mask, labels, ll, A, what=name)
 
 
 def test_every_tdt_row_reached_on_this_device():
-    rows = F.predicted_rows(_cus())
-    for obj, ks in F.expected_inventory().items():
-        for k in ks:
-            assert (obj, k) in rows or (obj, k) in F.UNREACHABLE, (obj, k)
+    assert_every_row_reached(F, G.cus())
 
 
 # ----------------------------------------------------------------------------- parity against the fp64 reference
@@ -271,11 +191,11 @@ def test_invalid_arguments():
     for durs in ((), (1, 1), (2, 1), (-1, 1), (0,), (0, 65), tuple(range(9))):
         D = len(durs)
         dur = (C.c_int * max(D, 1))(*durs)
-        lab, ttl, tll = _dev(labels, tl, ll)
+        lab, ttl, tll = dev(labels, tl, ll)
         ws = torch.empty(1 << 20, dtype=torch.uint8, device=DEV)
         costs = np.zeros(N, np.float32)
         st = t.lib().compute_tdt_loss(xd.data_ptr(), None, dur, D, 0.0, lab.data_ptr(), tll.data_ptr(), ttl.data_ptr(),
-                                      x.shape[3] - D, N, costs.ctypes.data, ws.data_ptr(), _opt(T, U), 0)
+                                      x.shape[3] - D, N, costs.ctypes.data, ws.data_ptr(), options(T, U), 0)
         assert st == 2, durs
     # lengths that do not fit the tensor: the cost marker -> INVALID_VALUE with host costs; the other sample is computed
     st, c, _ = call(xd, labels, np.array([T + 1, T], np.int32), ll, (0, 1, 2), "host")
@@ -336,7 +256,7 @@ def test_autograd_reductions(reduction):
     x, labels, tl, ll, mask = _problem("ag", "f32", N, T, U, A, durs, rng=rng, lengths=(tl, ll))
     x = torch.nan_to_num(x)
     xd = x.to(DEV).requires_grad_()
-    loss = TDTLoss(durs, blank=A - 1, sigma=0.05, reduction=reduction)(xd, *_dev(labels, tl, ll))
+    loss = TDTLoss(durs, blank=A - 1, sigma=0.05, reduction=reduction)(xd, *dev(labels, tl, ll))
     go = torch.tensor([0.7, -1.3, 2.0][:loss.numel()], device=DEV).view(loss.shape)
     (loss * go).sum().backward()
     w = go.detach().cpu().numpy().reshape(-1)

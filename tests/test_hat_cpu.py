@@ -2,9 +2,7 @@
 with hat_log_probs, a closed form and the gradient formula of include/rnnt_hat.h; and libwarprnnt_hat.so's C-ABI and code
 objects against include/rnnt_hat.h and tests/hat_forms.py."""
 import os
-import re
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -12,12 +10,11 @@ import pytest
 import torch
 
 from tests import hat_forms as F
+from tests import inventory as I
 from tests import hat_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "warp-transducer_amd", "lib")
-LIB = os.path.join(LIBDIR, "libwarprnnt_hat.so")
-HEADER = os.path.join(ROOT, "include", "rnnt_hat.h")
+LIB, HEADER = "libwarprnnt_hat.so", "rnnt_hat.h"
 
 
 def _tiny(seed, N=3):
@@ -104,60 +101,27 @@ def test_hat_log_probs_refuses_bad_blank():
             hat_log_probs(torch.zeros(1, 1, 1, 4), blank)
 
 
-def _need_lib():
-    if not os.path.exists(LIB):
-        pytest.skip("libwarprnnt_hat.so is not built")
-
-
-def _exports(path):
-    nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
-    out = subprocess.run([nm, "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
-    return {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-2] in ("T", "W")}
-
-
-def _declared(header):
-    return set(re.findall(r"^rnntStatus_t\s+(\w+)\(", open(os.path.join(ROOT, "include", header)).read(), re.M))
-
-
 def test_exports_equal_the_header():
-    _need_lib()
-    declared = _declared("rnnt_hat.h")
-    assert len(declared) == 4 and _exports(LIB) == declared
+    declared = I.declared(HEADER)
+    assert len(declared) == 4 and I.exports(I.need_lib(LIB)) == declared
 
 
 def test_other_libraries_exports_unchanged():
     """The pruned and TDT libraries export exactly their headers, and the main library nothing of this one."""
-    _need_lib()
+    I.need_lib(LIB)
     for lib, header in (("libwarprnnt_tdt.so", "rnnt_tdt.h"), ("libwarprnnt_pruned.so", "rnnt_pruned.h")):
-        assert _exports(os.path.join(LIBDIR, lib)) == _declared(header), lib
-    main = _exports(os.path.join(LIBDIR, "libwarprnnt.so"))
+        assert I.exports(os.path.join(I.LIBDIR, lib)) == I.declared(header), lib
+    main = I.exports(os.path.join(I.LIBDIR, "libwarprnnt.so"))
     assert "compute_rnnt_loss" in main and not any("hat" in s for s in main)
 
 
 def test_python_bindings_match_the_header():
     from warprnnt_pytorch import hat
-    assert set(hat.EXPORTS) == _declared("rnnt_hat.h")
+    assert set(hat.EXPORTS) == I.declared(HEADER)
 
 
 def test_code_objects_hold_exactly_the_table():
-    _need_lib()
-    from tests import test_kernel_inventory as I
-    import pathlib
-    import tempfile
-    readelf, cxxfilt = I._tool("llvm-readelf"), I._tool("llvm-cxxfilt") or shutil.which("c++filt")
-    if readelf is None or cxxfilt is None:
-        pytest.skip("needs llvm-readelf and a demangler")
-    tmp = pathlib.Path(tempfile.mkdtemp())
-    got = {}
-    for elf in I.code_objects(LIB):
-        names = I.kernel_names(elf, tmp, readelf, cxxfilt)
-        obj = "f64" if any("F64" in n for n in names) else "h16" if any("BF16" in n for n in names) else "f32"
-        assert obj not in got
-        got[obj] = names
-    want = F.expected_inventory()
-    assert set(got) == set(want)
-    for obj in want:
-        assert got[obj] == want[obj], (obj, sorted(got[obj] - want[obj]), sorted(want[obj] - got[obj]))
+    I.assert_side_inventory(I.need_lib(LIB), F.expected_inventory())
 
 
 def test_device_code_has_no_scratch():

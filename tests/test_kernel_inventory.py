@@ -5,54 +5,14 @@ rules (kernel_forms.predict, joint_forms.predict_joint); tests/test_gpu_kernel_f
 the cases and check on the GPU that they do."""
 import os
 import shutil
-import struct
-import subprocess
 
 import pytest
 
 from tests import joint_forms as J
 from tests import kernel_forms as K
+from tests.inventory import LIBDIR, _tool, code_objects, kernel_names
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "warp-transducer_amd", "lib", "libwarprnnt.so")
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
-
-
-def _tool(name):
-    for d in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin"),):
-        p = os.path.join(d, name)
-        if os.path.exists(p):
-            return p
-    return shutil.which(name)
-
-
-def code_objects(path):
-    """The gfx950 code objects (ELF images) of the offload bundles inside a shared library."""
-    data = open(path, "rb").read()
-    out, i = [], 0
-    while True:
-        i = data.find(MAGIC, i)
-        if i < 0:
-            return out
-        count, = struct.unpack_from("<Q", data, i + len(MAGIC))
-        p = i + len(MAGIC) + 8
-        for _ in range(count):
-            off, size, tl = struct.unpack_from("<QQQ", data, p)
-            triple = data[p + 24:p + 24 + tl].decode()
-            p += 24 + tl
-            if "amdgcn" in triple and size and data[i + off:i + off + 4] == b"\x7fELF":
-                out.append(data[i + off:i + off + size])
-        i += len(MAGIC)
-
-
-def kernel_names(elf, tmp_path, readelf, cxxfilt):
-    """Demangled names (without the parameter list) of the kernel descriptors (*.kd) of one code object."""
-    f = tmp_path / "co.elf"
-    f.write_bytes(elf)
-    syms = subprocess.run([readelf, "--symbols", "--wide", str(f)], capture_output=True, text=True, check=True).stdout
-    mangled = sorted({ln.split()[-1][:-3] for ln in syms.splitlines() if ln.split() and ln.split()[-1].endswith(".kd")})
-    dem = subprocess.run([cxxfilt], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout.split("\n")
-    return {d.split("(")[0].replace("void ", "", 1).strip() for d in dem if d.strip()}
+LIB = os.path.join(LIBDIR, "libwarprnnt.so")
 
 
 def classify(names):

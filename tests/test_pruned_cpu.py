@@ -1,21 +1,19 @@
 """No GPU: the pruned loss's references (tests/pruned_ref.py) against the existing ones, the prune-ranges rule's invariants, and
 libwarprnnt_pruned.so's C-ABI and code objects against include/rnnt_pruned.h and tests/pruned_forms.py."""
 import os
-import re
 import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from tests import inventory as I
 from tests import pruned_forms as P
 from tests import pruned_ref as R
 from tests.autograd_ref import rnnt_autograd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "warp-transducer_amd", "lib", "libwarprnnt_pruned.so")
-HEADER = os.path.join(ROOT, "include", "rnnt_pruned.h")
+LIB, HEADER = "libwarprnnt_pruned.so", "rnnt_pruned.h"
 
 
 def _problem(rng, N, T, U, A):
@@ -95,39 +93,13 @@ def test_has_path_brute_force():
     assert not R.has_path([0, 2], 2, 2, 2)                    # a gap between consecutive windows
 
 
-def _need_lib():
-    if not os.path.exists(LIB):
-        pytest.skip("libwarprnnt_pruned.so is not built")
-
-
 def test_exports_equal_the_header():
-    _need_lib()
-    declared = set(re.findall(r"^rnntStatus_t\s+(\w+)\(", open(HEADER).read(), re.M))
-    nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
-    out = subprocess.run([nm, "-D", "--defined-only", LIB], check=True, capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-2] in ("T", "W")}
+    declared, exported = I.declared(HEADER), I.exports(I.need_lib(LIB))
     assert declared and exported == declared, (sorted(exported), sorted(declared))
 
 
 def test_code_objects_hold_exactly_the_table():
-    _need_lib()
-    from tests import test_kernel_inventory as I
-    import pathlib
-    import tempfile
-    readelf, cxxfilt = I._tool("llvm-readelf"), I._tool("llvm-cxxfilt") or shutil.which("c++filt")
-    if readelf is None or cxxfilt is None:
-        pytest.skip("needs llvm-readelf and a demangler")
-    tmp = pathlib.Path(tempfile.mkdtemp())
-    got = {}
-    for elf in I.code_objects(LIB):
-        names = I.kernel_names(elf, tmp, readelf, cxxfilt)
-        obj = "f64" if any("F64" in n for n in names) else "h16" if any("BF16" in n for n in names) else "f32"
-        assert obj not in got
-        got[obj] = names
-    want = P.expected_inventory()
-    assert set(got) == set(want)
-    for obj in want:
-        assert got[obj] == want[obj], (obj, sorted(got[obj] - want[obj]), sorted(want[obj] - got[obj]))
+    I.assert_side_inventory(I.need_lib(LIB), P.expected_inventory())
 
 
 @pytest.fixture(scope="module")

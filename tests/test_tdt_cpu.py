@@ -1,21 +1,19 @@
 """No GPU: the TDT loss's fp64 reference (tests/tdt_ref.py) against brute-force path enumeration and a closed form, and
 libwarprnnt_tdt.so's C-ABI and code objects against include/rnnt_tdt.h and tests/tdt_forms.py."""
 import os
-import re
 import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+from tests import inventory as I
 from tests import tdt_forms as F
 from tests import tdt_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "warp-transducer_amd", "lib", "libwarprnnt_tdt.so")
-HEADER = os.path.join(ROOT, "include", "rnnt_tdt.h")
+LIB, HEADER = "libwarprnnt_tdt.so", "rnnt_tdt.h"
 SETS = [(0, 1, 2, 3, 4), (0, 2, 4), (1, 2), (1,)]
 
 
@@ -68,24 +66,14 @@ def test_single_duration_closed_form():
             assert abs(c[0] - want) < 1e-12, (fn, c, want)
 
 
-def _need_lib():
-    if not os.path.exists(LIB):
-        pytest.skip("libwarprnnt_tdt.so is not built")
-
-
 def test_exports_equal_the_header():
-    _need_lib()
-    declared = set(re.findall(r"^rnntStatus_t\s+(\w+)\(", open(HEADER).read(), re.M))
-    nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
-    out = subprocess.run([nm, "-D", "--defined-only", LIB], check=True, capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-2] in ("T", "W")}
+    declared, exported = I.declared(HEADER), I.exports(I.need_lib(LIB))
     assert declared and exported == declared, (sorted(exported), sorted(declared))
 
 
 def test_python_bindings_match_the_header():
     from warprnnt_pytorch import tdt
-    declared = set(re.findall(r"^rnntStatus_t\s+(\w+)\(", open(HEADER).read(), re.M))
-    assert set(tdt.EXPORTS) == declared
+    assert set(tdt.EXPORTS) == I.declared(HEADER)
 
 
 def test_python_refuses_bad_durations():
@@ -98,24 +86,7 @@ def test_python_refuses_bad_durations():
 
 
 def test_code_objects_hold_exactly_the_table():
-    _need_lib()
-    from tests import test_kernel_inventory as I
-    import pathlib
-    import tempfile
-    readelf, cxxfilt = I._tool("llvm-readelf"), I._tool("llvm-cxxfilt") or shutil.which("c++filt")
-    if readelf is None or cxxfilt is None:
-        pytest.skip("needs llvm-readelf and a demangler")
-    tmp = pathlib.Path(tempfile.mkdtemp())
-    got = {}
-    for elf in I.code_objects(LIB):
-        names = I.kernel_names(elf, tmp, readelf, cxxfilt)
-        obj = "f64" if any("F64" in n for n in names) else "h16" if any("BF16" in n for n in names) else "f32"
-        assert obj not in got
-        got[obj] = names
-    want = F.expected_inventory()
-    assert set(got) == set(want)
-    for obj in want:
-        assert got[obj] == want[obj], (obj, sorted(got[obj] - want[obj]), sorted(want[obj] - got[obj]))
+    I.assert_side_inventory(I.need_lib(LIB), F.expected_inventory())
 
 
 def test_device_code_has_no_scratch():
