@@ -1,7 +1,7 @@
 """The kernel forms of libwarprnnt_hat.so (csrc/rnnt_hat.hip, rnnt_hat_f64.hip, rnnt_hat_h16.hip): which kernels its three code
-objects hold, the release rules that pick them (a restatement of run_hat / launch_hat_stats / launch_lattice /
-launch_hat_coef / launch_hat_grad, csrc/rnnt_hat_impl.h and csrc/rnnt_host.h), and one case per form that reaches it -- the
-counterpart of tests/tdt_forms.py.  tests/test_hat_cpu.py checks the table against the built code objects;
+objects hold, the release rules that pick them (a restatement of run_hat / launch_hat_stats /
+launch_hat_grad, csrc/rnnt_hat_impl.h, and of launch_lattice / launch_coef, csrc/rnnt_host.h), and one case per form that
+reaches it -- the counterpart of tests/tdt_forms.py.  tests/test_hat_cpu.py checks the table against the built code objects;
 tests/test_gpu_hat.py runs every case and checks that exactly the predicted kernels ran.
 
 A case: dtype, N, T, U (= maxU), A, blank; `off` = byte offset of the logits and gradients from a 16-byte boundary (the

@@ -453,8 +453,6 @@ _ALL, _F32, _H16 = ("joint_f32", "joint_bf16", "joint_f16"), ("joint_f32",), ("j
 _PF = "the operand ping-pong is on (Tune::jfpf / jgpf = 1) for fp32 storage and for fewer than four columns per lane"
 _SPLIT_OH = "split_f needs maxU >= 64 and at most two column groups: A <= 64 (NKf = 1) or A <= 128 (NKf = 2, fp32 only)"
 UNREACHABLE = [
-    (_ALL, "rnnt::coef_kernel<float, false>", "the joint always hands launch_coef its correction sums (Tune::jfsum = 1): the "
-                                              "tiled form is coef_kernel<float, true>"),
     (_ALL, "rnnt::joint_df_kernel<{tag}, 1, false, false, false, false>", _PF),
     (_ALL, "rnnt::joint_df_kernel<{tag}, 2, false, false, false, false>", _PF),
     (_ALL, "rnnt::joint_df_kernel<{tag}, 1, true, false, true, false>",

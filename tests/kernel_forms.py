@@ -312,8 +312,6 @@ FORMS = [
 UNREACHABLE = {
     "rnnt::row_stats_tile_kernel<{tag}, 64>": "kTileMaxRowBytes = 4096 caps the lane group at 32 (64 needs rows > 6652 bytes)",
     "rnnt::row_stats_tile2d_kernel<{tag}, 8, 32>": "Tune::tile2d = 2 (16 x 16 tiles) in a release build; 8 x 32 is the dev-build A/B form",
-    "rnnt::coef_kernel<{lat}, true>": "the tiled coefficient kernel forming the additive joint's correction sums: launch_coef gets "
-                                      "`sums` from the joint path only",
 }
 # Kernels of the materialised objects outside the four stages, and where they are tested.
 OTHER = {

@@ -384,6 +384,37 @@ def test_benchmark_shapes(shape):
     _check("f32", c, g, rc, rg, mask, labels, ll, blank, what=shape)
 
 
+# ----------------------------------------------------------------------------- the record table's overlay (launch_coef)
+@pytest.mark.parametrize("form,U", [("cell", 48), ("tiled", 49)])
+def test_record_table_overlays_the_lattice_blocks(form, U):
+    """A record table past 32 MB (rnnt_host.h, make_layout) through the shared coefficient launcher: at maxU = 48 the
+    cell-per-thread kernel in groups of samples (N = 40 > group = 39: two launches, the second one's records on sample 0's
+    block), at maxU = 49 ONE launch of the tiled kernel with its overlay guard live (group = 38 < N).  No case of
+    tests/hat_forms.py reaches either: their tables are a few KB."""
+    from tests import kernel_forms as K
+    N, T, A, blank = 40, 1100, 3, 0
+    rec1 = T * U * 16
+    assert N * rec1 > K.ONE_GROUP_BYTES and K.ONE_GROUP_BYTES // rec1 == (39 if form == "cell" else 38)
+    groups = K.coef_launches(dict(dtype="f32", N=N, T=T, U=U, A=A), G.cus())       # (make_layout's group < N)
+    assert groups == 2
+    rng = np.random.default_rng(zlib.crc32(("overlay_" + form).encode()))
+    # Which records land on which block depends on maxT, maxU and N alone (every sample's T x U records are written, padding
+    # rows included): sample 0, whose block they land on, and the last sample, whose records do, are full; the others stay
+    # under 96 frames so that the fp64 reference (a Python loop over frames) takes a second
+    tl, ll = ragged_lengths(N, T, U, rng)
+    tl[1:-1] = np.minimum(tl[1:-1], rng.integers(1, 97, size=N - 2))
+    tl[-1], ll[-1] = T, U - 1
+    x, labels, tl, ll, mask = _problem("overlay_" + form, "f32", N, T, U, A, blank, rng=rng, lengths=(tl, ll))
+    gv = torch.full_like(x, float("nan")).to(DEV)
+    (st, c, g), names = profiled(lambda: call(x.to(DEV), labels, tl, ll, blank, "one", grads=gv))
+    assert st == 0
+    coef = [n for n in names if F.stage_of(n) == "coef"]
+    want = ["rnnt::coef_cell_kernel<float>"] * groups if form == "cell" else ["rnnt::coef_kernel<float, false>"]
+    assert coef == want, coef
+    rc, rg = _reference(x, labels, tl, ll, blank)
+    _check("f32", c, g, rc, rg, mask, labels, ll, blank, what="overlay " + form)
+
+
 # ----------------------------------------------------------------------------- 64-bit addressing
 def test_bf16_in_place_past_2_31_elements():
     """bf16 in place, N T U A > 2^31 elements: the last sample's in-lattice rows lie past element 2^31."""

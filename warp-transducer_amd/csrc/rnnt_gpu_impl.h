@@ -15,6 +15,7 @@
 #include "rnnt_align.h"
 #include "rnnt_cpu.h"
 #include "rnnt_host.h"
+#include "rnnt_profile.h"
 
 #include <atomic>
 #include <mutex>
@@ -159,19 +160,14 @@ static void launch_grad(Plan<typename Tag::comp>& p, const typename Tag::store* 
     const bool flat_ok = vec_ok && (pa & 15u) == 0 && (pg & 15u) == 0 && p.A <= (1 << 23) && (!tn.rows || packed);
     if (packed && !flat_ok) { p.failed = true; return; }   // (run_gpu has validated the alignment: not reached)
     if (flat_ok) {
-        const unsigned long long npk = E / V;
 #ifdef RNNT_DEV
         const int ppt = (tn.ppt == 1 || tn.ppt == 4) ? tn.ppt : 2;
 #else
         const int ppt = 2;
 #endif
-        const unsigned long long cpk = static_cast<unsigned long long>(ppt) * 256;
-        const unsigned long long nchunks = (npk + cpk - 1) / cpk;
-        const unsigned grid = static_cast<unsigned>(nchunks < static_cast<unsigned long long>(tn.gmax)
-                                                        ? (nchunks ? nchunks : 1) : tn.gmax);
-        const unsigned long long stride = static_cast<unsigned long long>(grid) * cpk * V;
-        const unsigned long long dq = stride / p.A;
-        const int drem = static_cast<int>(stride % p.A);
+        const FlatGrid fg = flat_grid(E / V, ppt, V);
+        const unsigned long long dq = fg.stride / p.A;
+        const int drem = static_cast<int>(fg.stride % p.A);
         const float invA = 1.0f / static_cast<float>(p.A);
         // packed + per-sample scale: one scale per packed row, in the (by now dead) alpha array of the workspace
         using CC = typename Tag::comp;
@@ -188,7 +184,7 @@ static void launch_grad(Plan<typename Tag::comp>& p, const typename Tag::store* 
                                rowscale, static_cast<long long>(p.packed_rows), p.padflag, recycled);
         }
 #define RNNT_FLAT(SC, PP, PS)                                                                                       \
-    hipLaunchKernelGGL((grad_flat_kernel<Tag, SC, PP, PS>), dim3(grid), dim3(256), 0, p.stream, acts, grads,        \
+    hipLaunchKernelGGL((grad_flat_kernel<Tag, SC, PP, PS>), dim3(fg.grid), dim3(256), 0, p.stream, acts, grads,     \
                        p.rowtab, grad_scale, E, R, p.A, p.blank, p.cells_per_sample, invA, dq, drem, rowscale, p.padflag)
         // padded rows are not read: always for long rows (the record is asked for first), for shorter ones when the
         // coefficient kernel has seen padding in this batch (packed layout: there are no padded rows)

@@ -3,11 +3,8 @@
 //     rnnt_hat.hip   F32 (+ every C entry point)     rnnt_hat_f64.hip   F64     rnnt_hat_h16.hip   BF16, F16
 // Statistics and gradient kernels are rnnt_hat_kernels.h's.  The workspace (make_layout: the record table overlaying the
 // per-sample lattice blocks), the plan, the lattice stage with its selection rule (launch_lattice) and the coefficient
-// kernels are rnnt_host.h's and rnnt_kernels.h's, instantiated here: HAT's lattice is the plain RNN-T lattice.
+// stage (launch_coef) are rnnt_host.h's and rnnt_kernels.h's, instantiated here: HAT's lattice is the plain RNN-T lattice.
 #pragma once
-// (rnnt_host.h's stage-timer, marker and additive-joint helpers are static and unused here: no profiling in this library)
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"
-#pragma clang diagnostic ignored "-Wunused-function"
 #include "rnnt_host.h"
 #include "rnnt_hat_kernels.h"
 #include "../../include/rnnt_hat.h"
@@ -40,46 +37,6 @@ static void launch_hat_stats(Plan<typename Tag::comp>& p, const typename Tag::st
     p.check();
 }
 
-// Stage 3: rnnt_host.h's launch_coef without the additive joint's forms (this library holds only what it launches): the
-// cell-per-thread kernel in groups of samples for maxU <= 48, else ONE launch of the tiled kernel with its overlay guard.
-template <typename C> static void launch_hat_coef(Plan<C>& p) {
-    const size_t rec1 = static_cast<size_t>(p.cells_per_sample) * sizeof(Cell<C>);
-    auto recycled_after = [&](int b_end) -> int {
-        const size_t end = rec1 * static_cast<size_t>(b_end);
-        if (end <= p.head_bytes || p.block_bytes == 0) return 0;
-        return static_cast<int>((end - p.head_bytes + p.block_bytes - 1) / p.block_bytes);
-    };
-    if (!coef_is_tiled(p)) {
-        const int step = p.overlay && p.coef_group > 0 && p.coef_group < kGridSamples ? p.coef_group : kGridSamples;
-        const long long skew_cells = static_cast<long long>(p.maxT + p.maxU - 1) * ((p.Up + 63) / 64) * 64;
-        for (int b0 = 0; b0 < p.N; b0 += step) {
-            const int nb = p.N - b0 < step ? p.N - b0 : step;
-            const dim3 cgrid(static_cast<unsigned>(((skew_cells + 255) / 256 + 7) / 8 * 8), nb);
-            hipLaunchKernelGGL((coef_cell_kernel<C>), cgrid, dim3(256), 0, p.stream, p.lp2, p.logz, p.alpha, p.beta, p.offa,
-                               p.offb, p.llf, p.labels, p.input_lengths, p.label_lengths, p.rowtab, p.maxT, p.maxU, p.Up,
-                               static_cast<float*>(nullptr), joint_upad(p.maxU), 0.0f, 1, static_cast<const long long*>(nullptr),
-                               p.lat_w, p.lat_sh, b0, p.N, p.padflag, recycled_after(b0 + nb));
-        }
-    } else {
-        const int DN = sizeof(C) == 4 ? 32 : 16;           // diagonals per tile (coef_kernel)
-        const int tilesU = (p.maxU + 63) / 64, tilesN = (p.maxT + p.maxU - 1 + DN - 1) / DN;
-        int* const done = p.overlay ? p.coef_done : nullptr;
-        const int slice = 0x7fffffff / (tilesU * tilesN) < kGridSamples ? 0x7fffffff / (tilesU * tilesN) : kGridSamples;
-        for (int b0 = 0; b0 < p.N; b0 += slice) {
-            const int nb = p.N - b0 < slice ? p.N - b0 : slice;
-            const dim3 cgrid(static_cast<unsigned>(tilesU * tilesN) * static_cast<unsigned>(nb));
-            hipLaunchKernelGGL((coef_kernel<C, false>), cgrid, dim3(256), 0, p.stream, p.lp2, p.logz, p.alpha, p.beta, p.offa,
-                               p.offb, p.llf, p.labels, p.input_lengths, p.label_lengths, p.rowtab, p.maxT, p.maxU, p.Up,
-                               static_cast<float*>(nullptr), joint_upad(p.maxU), tilesU, 0.0f, 1,
-                               static_cast<const long long*>(nullptr), p.lat_w, p.lat_sh, b0, p.N, p.padflag,
-                               static_cast<float*>(nullptr), static_cast<float*>(nullptr), static_cast<float*>(nullptr),
-                               static_cast<int*>(nullptr), recycled_after(b0 + nb), done, static_cast<unsigned long long>(rec1),
-                               static_cast<unsigned long long>(p.head_bytes), static_cast<unsigned long long>(p.block_bytes), 0);
-        }
-    }
-    p.check();
-}
-
 // Stage 4: the flat packet stream when both tensors sit on 16-byte boundaries, else element by element
 template <typename Tag>
 static void launch_hat_grad(Plan<typename Tag::comp>& p, const typename Tag::store* acts, typename Tag::store* grads,
@@ -90,14 +47,10 @@ static void launch_hat_grad(Plan<typename Tag::comp>& p, const typename Tag::sto
     const unsigned long long E = static_cast<unsigned long long>(R) * p.A;
     const uintptr_t pa = reinterpret_cast<uintptr_t>(acts), pg = reinterpret_cast<uintptr_t>(grads);
     if (((pa | pg) & 15u) == 0) {
-        const unsigned long long cpk = 2 * 256;                        // packets per chunk (hat_grad_kernel: PPT = 2)
-        const unsigned long long nchunks = (E / V + cpk - 1) / cpk;
-        const unsigned grid = static_cast<unsigned>(nchunks < static_cast<unsigned long long>(tune().gmax)
-                                                        ? (nchunks ? nchunks : 1) : tune().gmax);
-        const unsigned long long stride = static_cast<unsigned long long>(grid) * cpk * V;
-        hipLaunchKernelGGL((hat_grad_kernel<Tag>), dim3(grid), dim3(256), 0, p.stream, acts, grads, p.rowtab, grad_scale, E,
-                           R, p.A, p.blank, TU, 1.0f / static_cast<float>(p.A), stride / p.A,
-                           static_cast<int>(stride % p.A), p.padflag);
+        const FlatGrid fg = flat_grid(E / V, 2, V);                    // (hat_grad_kernel: PPT = 2)
+        hipLaunchKernelGGL((hat_grad_kernel<Tag>), dim3(fg.grid), dim3(256), 0, p.stream, acts, grads, p.rowtab, grad_scale, E,
+                           R, p.A, p.blank, TU, 1.0f / static_cast<float>(p.A), fg.stride / p.A,
+                           static_cast<int>(fg.stride % p.A), p.padflag);
     } else {
         const unsigned long long blocks = (E + 255) / 256;
         const unsigned grid = static_cast<unsigned>(blocks < 65536 ? (blocks ? blocks : 1) : 65536);
@@ -133,18 +86,11 @@ rnntStatus_t run_hat(const typename Tag::store* acts, typename Tag::store* grads
     if (do_fwd) {
         launch_hat_stats<Tag>(p, acts);
         if (!p.failed) launch_lattice(p, want_grad);
-        if (!p.failed && want_grad) launch_hat_coef(p);
+        if (!p.failed && want_grad) launch_coef(p);
     }
     if (do_bwd && !p.failed) launch_hat_grad<Tag>(p, acts, grads, grad_scale);
     if (p.failed) return RNNT_STATUS_EXECUTION_FAILED;
-    if (costs_host != nullptr) {
-        if (hipMemcpyAsync(costs_host, p.costs_dev, sizeof(C) * N, hipMemcpyDeviceToHost, p.stream) != hipSuccess)
-            return RNNT_STATUS_MEMOPS_FAILED;
-        if (hipStreamSynchronize(p.stream) != hipSuccess) return RNNT_STATUS_EXECUTION_FAILED;
-        for (int b = 0; b < N; ++b)
-            if (is_cost_invalid<C>(costs_host[b])) return RNNT_STATUS_INVALID_VALUE;
-    }
-    return RNNT_STATUS_SUCCESS;
+    return costs_host != nullptr ? finish_host_costs(costs_host, p.costs_dev, N, p.stream) : RNNT_STATUS_SUCCESS;
 }
 
 }  // namespace rnnt

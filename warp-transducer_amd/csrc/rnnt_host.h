@@ -1,21 +1,21 @@
-// rnnt_host.h -- what the two host translation units of the library share: workspace layout, stage timers, tuning
-// constants, the launch plan, and the launchers of the two stages both paths run (lattice, coefficients).
+// rnnt_host.h -- what the host translation units of the main library and of the side libraries (pruned, TDT, HAT) share:
+// workspace layout, tuning constants, the launch plan, the launchers of the two stages every lattice path runs (lattice,
+// coefficients), and the small host helpers of the drivers (flat_grid, finish_host_costs, is_device_pointer, bad_args).
 //   rnnt_gpu.hip    the materialised path (row statistics ... gradient stream) and the C entry points of rnnt.h
 //   rnnt_joint.hip  the additive-joint path and its entry points (compute_rnnt_loss_add*)
 // Two translation units = two code objects: HIP loads a code object on the first launch of one of its kernels, and the
 // additive-joint kernels are 45 % of the library's device code -- a caller of compute_rnnt_loss does not pay for loading
-// them (first call of a process: tools/first_call.py).  Everything here is static / template code, compiled into both.
+// them (first call of a process: tools/first_call.py).  Everything here is static / inline / template code, compiled into each;
+// a unit instantiates -- and its code object holds -- only the kernels of the launchers it calls.  The stage timers and
+// roctx ranges of the main library are rnnt_profile.h's.
 #pragma once
 
 #include <atomic>
 #include <hip/hip_runtime.h>
 
-#include <dlfcn.h>
-
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 
 #include "../../include/rnnt.h"
 #include "rnnt_kernels.h"
@@ -55,7 +55,7 @@ constexpr int kCoefGroups = 8;
 // lat = bytes of one lattice value (4: fp32 lattice for 16/32-bit activations, 8: fp64).
 // joint: also the additive-joint planes (get_workspace_size_add); they sit BEHIND everything the
 // materialised path uses, so a plan carved with joint = true is valid for both.
-static Layout make_layout(int maxT, int maxU, int N, size_t lat, bool joint) {
+static inline Layout make_layout(int maxT, int maxU, int N, size_t lat, bool joint) {
     const size_t D = lat_rows(maxT, maxU);      // diagonals + padding rows
     const size_t Up = lat_stride(maxU);         // row stride of the skewed arrays
     const size_t W = (Up + 63) / 64;            // wavefronts of a lattice block at one column per lane
@@ -112,130 +112,6 @@ static Layout make_layout(int maxT, int maxU, int N, size_t lat, bool joint) {
     }
     l.total = o + kAlign;                       // slack to align the caller's base pointer
     return l;
-}
-
-// ----------------------------------------------------------------------------- profiling
-// Stage boundaries as HIP events on the caller's stream: 0 start, 1 after the statistics, 2 after the lattice, 3 after
-// the coefficients (end of a forward phase), 4 start and 5 end of the gradient stage.  A one-call entry records all six;
-// the two-phase entries record 0-3 (compute_rnnt_loss_fwd) and 4-5 (compute_rnnt_loss_bwd), and whatever the caller
-// enqueues between the two calls is in neither stage.  One rnnt_profile_collect() reads what has been recorded since
-// the last one as ONE step.
-struct Profile {
-    std::atomic<bool> on{false};   // read without the mutex to decide whether to take it; everything else below is guarded by g_prof_mu
-    bool ready = false;
-    hipEvent_t ev[6];
-    double ms[5] = {0, 0, 0, 0, 0};   // statistics, lattice, coefficients, gradient, first event to last
-    int calls = 0;
-    bool pending = false;   // events of an asynchronous call recorded, not yet read
-    bool has_fwd = false, has_bwd = false;
-    // A call in the two-half schedule (rnnt_set_aux_stream, run_gpu) records these instead of ev[1..4]: on the caller's stream
-    // h0 / h1 = {before the half's statistics, after them, before its coefficients, after them, after its gradient kernel};
-    // on the auxiliary stream the start and end of each half's lattice kernel.
-    bool split = false;
-    hipEvent_t hev[2][5], lev[2][2];
-};
-extern Profile g_prof;     // one instance for the library (defined in rnnt_gpu.hip)
-extern std::mutex g_prof_mu;   // held by a profiled call from its first event record to its last, and by the
-                               // rnnt_profile_* entries: concurrent callers cannot tear the shared event set (their
-                               // calls are serialised while the timers are on; off -- the default -- nobody takes it)
-
-// `locked`: the caller holds g_prof_mu (it took it because it saw `on`); without the lock nothing of the shared event set is touched
-static bool prof_prepare(bool locked) {
-    if (!locked || !g_prof.on.load(std::memory_order_relaxed)) return false;   // (switched off between the caller's test and its lock: a plain, unprofiled call)
-    if (!g_prof.ready) {
-        for (auto& e : g_prof.ev)
-            if (hipEventCreate(&e) != hipSuccess) return false;
-        for (auto& h : g_prof.hev) for (auto& e : h) if (hipEventCreate(&e) != hipSuccess) return false;
-        for (auto& h : g_prof.lev) for (auto& e : h) if (hipEventCreate(&e) != hipSuccess) return false;
-        g_prof.ready = true;
-    }
-    return true;
-}
-
-// mark(i) of the run_* functions: i = 0..4 are the boundaries of the four stages of one call
-static void prof_mark(int i, bool do_fwd, bool do_bwd, hipStream_t stream) {
-    if (i < 3) { if (do_fwd) (void)hipEventRecord(g_prof.ev[i], stream); return; }
-    if (i == 3) {
-        if (do_fwd) { (void)hipEventRecord(g_prof.ev[3], stream); g_prof.has_fwd = true; }
-        if (do_bwd) (void)hipEventRecord(g_prof.ev[4], stream);
-        return;
-    }
-    if (do_bwd) { (void)hipEventRecord(g_prof.ev[5], stream); g_prof.has_bwd = true; }
-}
-
-static inline void prof_accumulate() {
-    float ms = 0.f;
-    if (g_prof.split) {
-        // two-half schedule: statistics, coefficients and gradient = the sums over the halves (they run back to back on the
-        // caller's stream); lattice = what the auxiliary stream spent on it, CONCURRENTLY with the other half's streaming
-        // kernels -- it is not part of the critical path, ms[4] (first event to last) is
-        auto add = [&](double& acc, hipEvent_t a, hipEvent_t b) { if (hipEventElapsedTime(&ms, a, b) == hipSuccess) acc += ms; };
-        for (int h = 0; h < 2; ++h) {
-            add(g_prof.ms[0], g_prof.hev[h][0], g_prof.hev[h][1]);
-            add(g_prof.ms[1], g_prof.lev[h][0], g_prof.lev[h][1]);
-            if (g_prof.has_fwd && g_prof.has_bwd) {
-                add(g_prof.ms[2], g_prof.hev[h][2], g_prof.hev[h][3]);
-                add(g_prof.ms[3], g_prof.hev[h][3], g_prof.hev[h][4]);
-            } else if (g_prof.has_fwd) {
-                add(g_prof.ms[2], g_prof.hev[h][2], g_prof.hev[h][3]);
-            }
-        }
-        add(g_prof.ms[4], g_prof.hev[0][0], g_prof.hev[1][g_prof.has_bwd ? 4 : 3]);
-        g_prof.calls++;
-        g_prof.pending = g_prof.has_fwd = g_prof.has_bwd = g_prof.split = false;
-        return;
-    }
-    if (g_prof.has_fwd)
-        for (int i = 0; i < 3; ++i)
-            if (hipEventElapsedTime(&ms, g_prof.ev[i], g_prof.ev[i + 1]) == hipSuccess) g_prof.ms[i] += ms;
-    if (g_prof.has_bwd && hipEventElapsedTime(&ms, g_prof.ev[4], g_prof.ev[5]) == hipSuccess) g_prof.ms[3] += ms;
-    if ((g_prof.has_fwd || g_prof.has_bwd) &&
-        hipEventElapsedTime(&ms, g_prof.ev[g_prof.has_fwd ? 0 : 4], g_prof.ev[g_prof.has_bwd ? 5 : 3]) == hipSuccess)
-        g_prof.ms[4] += ms;
-    g_prof.calls++;
-    g_prof.pending = g_prof.has_fwd = g_prof.has_bwd = false;
-}
-
-// ----------------------------------------------------------------------------- stage ranges for external profilers
-// rocprofv3 --kernel-trace shows kernel names only; with ranges on (rnnt_profile_enable bit 1, or WARPRNNT_ROCTX=1 in the
-// environment) every call brackets the ENQUEUE of its four stages with roctx ranges -- the counterpart of the reference's
-// DEBUG_TIME stage timers (include/detail/gpu_rnnt.h:112-122) -- which `rocprofv3 --marker-trace` puts on the same
-// timeline as the kernels.  The marker library is looked up at run time (librocprofiler-sdk-roctx, else libroctx64):
-// the library does not link against a profiler, and without one the switch does nothing.
-struct Ranges {
-    std::atomic<int> mode{-1};     // -1: not decided (environment), 0 off, 1 on
-    std::once_flag resolved;       // the two entry points below are written once, inside call_once, and only read afterwards
-    int (*push)(const char*) = nullptr;
-    int (*pop)() = nullptr;
-};
-extern Ranges g_ranges;            // one instance for the library (defined in rnnt_gpu.hip)
-
-static bool ranges_prepare() {
-    int mode = g_ranges.mode.load(std::memory_order_relaxed);
-    if (mode < 0) {
-        const char* e = getenv("WARPRNNT_ROCTX");
-        int expected = -1;
-        mode = (e != nullptr && atoi(e) > 0) ? 1 : 0;
-        if (!g_ranges.mode.compare_exchange_strong(expected, mode, std::memory_order_relaxed)) mode = expected;   // (rnnt_profile_enable got there first)
-    }
-    if (mode != 1) return false;
-    std::call_once(g_ranges.resolved, [] {          // concurrent first calls: one resolves, the others wait; both pointers or neither
-        for (const char* name : {"librocprofiler-sdk-roctx.so.1", "librocprofiler-sdk-roctx.so", "libroctx64.so.4", "libroctx64.so"}) {
-            void* h = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-            if (h == nullptr) continue;
-            auto push = reinterpret_cast<int (*)(const char*)>(dlsym(h, "roctxRangePushA"));
-            auto pop = reinterpret_cast<int (*)()>(dlsym(h, "roctxRangePop"));
-            if (push != nullptr && pop != nullptr) { g_ranges.push = push; g_ranges.pop = pop; break; }
-        }
-    });
-    return g_ranges.push != nullptr;
-}
-
-// boundary i of a call (the same five as prof_mark): closes stage i-1, opens stage i
-static void ranges_mark(int i, bool do_fwd, bool do_bwd, const char* const names[4]) {
-    auto active = [&](int stage) { return stage >= 0 && stage < 4 && (stage < 3 ? do_fwd : do_bwd); };
-    if (active(i - 1)) (void)g_ranges.pop();
-    if (active(i)) (void)g_ranges.push(names[i]);
 }
 
 // ----------------------------------------------------------------------------- tuning knobs
@@ -429,21 +305,29 @@ template <typename C> static void launch_lattice(Plan<C>& p, bool with_beta) {
     p.check();
 }
 
-// Stage 3: gradient coefficients per row into the natural-order row table.
-// joint: the additive-joint path (dense planes for its gradient GEMMs); sums != nullptr: also their correction sums
-// {sfb, sgb, sgl, farflag} -- formed inside the tiled kernel; returns false when the caller still has to run
-// joint_sums_kernel (the cell-per-thread form of small lattices leaves them to it)
+// Stage 3: gradient coefficients per row into the natural-order row table.  The ONE coefficient launcher of the project: the
+// materialised path, the pruned loss and HAT call launch_coef(p); the additive joint calls launch_coef<C, true>.
+// JOINT = false: records only (no planes; `onehot` and `sums` are not looked at) -- instantiates coef_cell_kernel<C> and
+//   coef_kernel<C, false>, nothing else.
+// JOINT = true: the additive-joint path (dense planes for its gradient GEMMs) -- coef_cell_kernel<C> and coef_kernel<C, true>,
+//   which also forms their correction sums {sfb, sgb, sgl, farflag} from `sums`; returns false when the caller still has to
+//   run joint_sums_kernel (the cell-per-thread form of small lattices leaves them to it).  The tiled form without sums
+//   (Tune::jfsum = 0, an A/B switch) exists in the development build only: a release build fails the plan instead.
 struct JointSums { float *sfb, *sgb, *sgl; int* farflag; };
 template <typename C> static bool coef_is_tiled(const Plan<C>& p) { return !(p.maxU <= 48 || !tune().ctile); }
-template <typename C> static bool launch_coef(Plan<C>& p, bool joint = false, bool onehot = false, const JointSums* sums = nullptr) {
-    float* wmat = joint ? p.wmat : nullptr;
+template <typename C, bool JOINT = false> static bool launch_coef(Plan<C>& p, bool onehot = false, const JointSums* sums = nullptr) {
+    float* wmat = nullptr;
     const int Upad = joint_upad(p.maxU);
-    // additive joint: W and CL planes always (the DF kernel takes its label corrections from CL); small
-    // vocabularies add CB and drop the records (a far cell's c is kept in their memory)
-    int planes = onehot ? joint_planes_onehot(p.maxU) : (joint ? 2 : 1);
-    // the tiled kernel forming the sums itself: nothing reads cb per cell (joint_df_kernel<..., BS> and the epilogue form both take
-    // the row sums) nor the records -- W and CL only, whatever the vocabulary
-    if (coef_is_tiled(p) && sums != nullptr && joint_planes_onehot(p.maxU) == 4 && tune().jnocb) planes = 5;
+    int planes = 1;
+    if constexpr (JOINT) {
+        wmat = p.wmat;
+        // additive joint: W and CL planes always (the DF kernel takes its label corrections from CL); small
+        // vocabularies add CB and drop the records (a far cell's c is kept in their memory)
+        planes = onehot ? joint_planes_onehot(p.maxU) : 2;
+        // the tiled kernel forming the sums itself: nothing reads cb per cell (joint_df_kernel<..., BS> and the epilogue form both take
+        // the row sums) nor the records -- W and CL only, whatever the vocabulary
+        if (coef_is_tiled(p) && sums != nullptr && joint_planes_onehot(p.maxU) == 4 && tune().jnocb) planes = 5;
+    }
     // Launches of at most `coef_group` samples, in stream order: the records of a group overlay the lattice blocks of the
     // samples in front of it, which are dead by then (make_layout).  `recycled`: how many blocks, counted from sample 0 of
     // the WHOLE batch, lie under the records written so far -- left in the workspace for compute_rnnt_loss_lattice_dump.
@@ -465,6 +349,10 @@ template <typename C> static bool launch_coef(Plan<C>& p, bool joint = false, bo
                                wmat, Upad, p.fastemit, planes, p.offsets, p.lat_w, p.lat_sh, b0, p.N, p.padflag, recycled_after(b0 + nb));
         }
     } else {
+        const bool with_sums = JOINT && sums != nullptr;
+#ifndef RNNT_DEV
+        if (JOINT && !with_sums) { p.failed = true; return false; }   // (not reached: Tune::jfsum = 1 in a release build)
+#endif
         const int DN = sizeof(C) == 4 ? 32 : 16;           // diagonals per tile (coef_kernel)
         const int tilesU = (p.maxU + 63) / 64, tilesN = (p.maxT + p.maxU - 1 + DN - 1) / DN;
         // ONE launch (slices of 65535 samples), the overlay guarded inside the kernel
@@ -475,25 +363,64 @@ template <typename C> static bool launch_coef(Plan<C>& p, bool joint = false, bo
             const int nb = p.N - b0 < slice ? p.N - b0 : slice;
             const int recycled = recycled_after(b0 + nb);
             const dim3 cgrid(static_cast<unsigned>(tilesU * tilesN) * static_cast<unsigned>(nb));   // one-dimensional, sample-major (coef_kernel)
-            if (sums != nullptr)
-                hipLaunchKernelGGL((coef_kernel<C, true>), cgrid, dim3(256), 0, p.stream, p.lp2, p.logz, p.alpha, p.beta, p.offa,
-                                   p.offb, p.llf, p.labels, p.input_lengths, p.label_lengths, p.rowtab, p.maxT, p.maxU, p.Up,
-                                   wmat, Upad, tilesU, p.fastemit, planes, p.offsets, p.lat_w, p.lat_sh, b0, p.N, p.padflag,
-                                   sums->sfb, sums->sgb, sums->sgl, sums->farflag, recycled, done, static_cast<unsigned long long>(rec1),
-                                   head_arg, static_cast<unsigned long long>(p.block_bytes), p.first_sample);
-            else
-                hipLaunchKernelGGL((coef_kernel<C, false>), cgrid, dim3(256), 0, p.stream, p.lp2, p.logz, p.alpha, p.beta, p.offa,
-                                   p.offb, p.llf, p.labels, p.input_lengths, p.label_lengths, p.rowtab, p.maxT, p.maxU, p.Up,
-                                   wmat, Upad, tilesU, p.fastemit, planes, p.offsets, p.lat_w, p.lat_sh, b0, p.N, p.padflag,
-                                   static_cast<float*>(nullptr), static_cast<float*>(nullptr), static_cast<float*>(nullptr),
-                                   static_cast<int*>(nullptr), recycled, done, static_cast<unsigned long long>(rec1),
-                                   head_arg, static_cast<unsigned long long>(p.block_bytes), p.first_sample);
+#define RNNT_COEF(SUMS, SFB, SGB, SGL, FAR)                                                                                 \
+    hipLaunchKernelGGL((coef_kernel<C, SUMS>), cgrid, dim3(256), 0, p.stream, p.lp2, p.logz, p.alpha, p.beta, p.offa,       \
+                       p.offb, p.llf, p.labels, p.input_lengths, p.label_lengths, p.rowtab, p.maxT, p.maxU, p.Up,           \
+                       wmat, Upad, tilesU, p.fastemit, planes, p.offsets, p.lat_w, p.lat_sh, b0, p.N, p.padflag,            \
+                       SFB, SGB, SGL, FAR, recycled, done, static_cast<unsigned long long>(rec1),                           \
+                       head_arg, static_cast<unsigned long long>(p.block_bytes), p.first_sample)
+#define RNNT_COEF_PLAIN                                                                                                     \
+    RNNT_COEF(false, static_cast<float*>(nullptr), static_cast<float*>(nullptr), static_cast<float*>(nullptr),              \
+              static_cast<int*>(nullptr))
+            if constexpr (JOINT) {
+#ifdef RNNT_DEV
+                if (!with_sums) RNNT_COEF_PLAIN; else
+#endif
+                RNNT_COEF(true, sums->sfb, sums->sgb, sums->sgl, sums->farflag);
+            } else {
+                RNNT_COEF_PLAIN;
+            }
+#undef RNNT_COEF_PLAIN
+#undef RNNT_COEF
         }
         p.check();
-        return sums != nullptr;
+        return with_sums;
     }
     p.check();
     return false;
+}
+
+// Grid of a flat gradient stream (grad_flat_kernel, pruned_ / tdt_ / hat_grad_kernel): `packets` 16-byte packets of `vec`
+// elements, `ppt` packets per thread of a 256-thread block, a block per chunk up to Tune::gmax blocks; `stride` = elements
+// the whole grid advances per round (the launcher divides it by its own row width).
+struct FlatGrid { unsigned grid; unsigned long long stride; };
+static inline FlatGrid flat_grid(unsigned long long packets, int ppt, int vec) {
+    const unsigned long long cpk = static_cast<unsigned long long>(ppt) * 256;         // packets per chunk
+    const unsigned long long nchunks = (packets + cpk - 1) / cpk;
+    const unsigned grid = static_cast<unsigned>(nchunks < static_cast<unsigned long long>(tune().gmax)
+                                                    ? (nchunks ? nchunks : 1) : tune().gmax);
+    return {grid, static_cast<unsigned long long>(grid) * cpk * vec};
+}
+
+// Tail of a one-call entry with costs in host memory: the N costs copied behind the last kernel, the stream synchronised,
+// a cost marker (device-side lengths that do not fit the tensor) answered with RNNT_STATUS_INVALID_VALUE.
+template <typename C> rnntStatus_t finish_host_costs(C* costs_host, const C* costs_dev, int N, hipStream_t stream) {
+    if (hipMemcpyAsync(costs_host, costs_dev, sizeof(C) * N, hipMemcpyDeviceToHost, stream) != hipSuccess)
+        return RNNT_STATUS_MEMOPS_FAILED;
+    if (hipStreamSynchronize(stream) != hipSuccess) return RNNT_STATUS_EXECUTION_FAILED;
+    for (int b = 0; b < N; ++b)
+        if (is_cost_invalid<C>(costs_host[b])) return RNNT_STATUS_INVALID_VALUE;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// Host memory (pageable or pinned) or device memory?  The one-call entries of the side libraries copy host costs behind
+// their last kernel.
+inline bool is_device_pointer(const void* p) {
+    hipPointerAttribute_t attr;
+    const bool dev = hipPointerGetAttributes(&attr, p) == hipSuccess &&
+                     (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged);
+    (void)hipGetLastError();                       // (the query of a pageable pointer reports an error: not ours)
+    return dev;
 }
 
 // options.loc as the int a caller really passed: a C program or ctypes can put ANY value there, and loading one outside the

@@ -9,6 +9,7 @@
 
 #include "rnnt_align.h"
 #include "rnnt_host.h"
+#include "rnnt_profile.h"
 #include "rnnt_joint_kernels.h"
 #include "rnnt_joint16_kernels.h"
 
@@ -189,7 +190,7 @@ rnntStatus_t run_gpu_joint(const typename Tag::store* f, const typename Tag::sto
     if (do_fwd && training) {
         const JointSums sums{sfb, sgb, sgl, farflag};
         // (the tiled coefficient kernel forms the correction sums itself; the cell-per-thread form leaves them to a pass of their own)
-        if (!launch_coef(p, /*joint=*/true, onehot, tune().jfsum ? &sums : nullptr))
+        if (!launch_coef<float, true>(p, onehot, tune().jfsum ? &sums : nullptr))
             hipLaunchKernelGGL(joint_sums_kernel<0>, fixgrid, dim3(256), 0, p.stream, p.rowtab, input_lengths, label_lengths, sfb,
                                sgb, sgl, farflag, maxT, maxU, N, cplanes, joint_upad(maxU));
         p.check();

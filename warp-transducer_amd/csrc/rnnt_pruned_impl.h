@@ -5,8 +5,6 @@
 // The lattice, the coefficient stage and the additive joint's partition stage are the launchers of rnnt_host.h /
 // rnnt_joint_impl.h, unchanged; the two streaming stages of the pruned loss and the ranges kernels are rnnt_pruned_kernels.h.
 #pragma once
-// (rnnt_host.h's stage-timer and marker helpers are static and unused here: no profiling in this library)
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"
 #include "rnnt_host.h"
 #include "rnnt_joint_impl.h"
 #include "rnnt_pruned_kernels.h"
@@ -55,14 +53,10 @@ static void launch_pruned_grad(Plan<typename Tag::comp>& p, const typename Tag::
     const unsigned long long E = R * p.A;
     const uintptr_t pa = reinterpret_cast<uintptr_t>(acts), pg = reinterpret_cast<uintptr_t>(grads);
     if (((pa | pg) & 15u) == 0 && p.A <= (1 << 23)) {
-        const unsigned long long cpk = 2 * 256;                        // packets per chunk (pruned_grad_kernel: PPT = 2)
-        const unsigned long long nchunks = (E / V + cpk - 1) / cpk;
-        const unsigned grid = static_cast<unsigned>(nchunks < static_cast<unsigned long long>(tune().gmax)
-                                                        ? (nchunks ? nchunks : 1) : tune().gmax);
-        const unsigned long long stride = static_cast<unsigned long long>(grid) * cpk * V;
-        hipLaunchKernelGGL((pruned_grad_kernel<Tag>), dim3(grid), dim3(256), 0, p.stream, acts, grads, p.rowtab, win,
-                           grad_scale, E, p.A, p.blank, S, p.maxT, p.maxU, 1.0f / static_cast<float>(p.A), stride / p.A,
-                           static_cast<int>(stride % p.A));
+        const FlatGrid fg = flat_grid(E / V, 2, V);                    // (pruned_grad_kernel: PPT = 2)
+        hipLaunchKernelGGL((pruned_grad_kernel<Tag>), dim3(fg.grid), dim3(256), 0, p.stream, acts, grads, p.rowtab, win,
+                           grad_scale, E, p.A, p.blank, S, p.maxT, p.maxU, 1.0f / static_cast<float>(p.A), fg.stride / p.A,
+                           static_cast<int>(fg.stride % p.A));
     } else {
         const unsigned long long blocks = (E + 255) / 256;
         const unsigned grid = static_cast<unsigned>(blocks < 65536 ? (blocks ? blocks : 1) : 65536);
@@ -116,14 +110,7 @@ rnntStatus_t run_pruned(const typename Tag::store* acts, typename Tag::store* gr
     }
     if (do_bwd) launch_pruned_grad<Tag>(p, acts, grads, grad_scale, win, S);
     if (p.failed) return RNNT_STATUS_EXECUTION_FAILED;
-    if (costs_host != nullptr) {
-        if (hipMemcpyAsync(costs_host, p.costs_dev, sizeof(C) * N, hipMemcpyDeviceToHost, p.stream) != hipSuccess)
-            return RNNT_STATUS_MEMOPS_FAILED;
-        if (hipStreamSynchronize(p.stream) != hipSuccess) return RNNT_STATUS_EXECUTION_FAILED;
-        for (int b = 0; b < N; ++b)
-            if (is_cost_invalid<C>(costs_host[b])) return RNNT_STATUS_INVALID_VALUE;
-    }
-    return RNNT_STATUS_SUCCESS;
+    return costs_host != nullptr ? finish_host_costs(costs_host, p.costs_dev, N, p.stream) : RNNT_STATUS_SUCCESS;
 }
 
 // Prune ranges of the additive joint: its partition stage (row maxima, Z: lp2 / log Z of every cell), the lattice in both

@@ -4,11 +4,6 @@
 #include "rnnt_tdt_impl.h"
 
 namespace rnnt {
-// the state rnnt_host.h declares (the main library's copies are hidden inside it; this library never turns them on)
-Profile g_prof;
-std::mutex g_prof_mu;
-Ranges g_ranges;
-
 template rnntStatus_t run_tdt<F32>(const float*, float*, const float*, const int*, int, float, const int*, const int*,
                                    const int*, int, int, float*, float*, void*, const rnntOptions&, int, bool);
 }  // namespace rnnt
@@ -16,15 +11,6 @@ template rnntStatus_t run_tdt<F32>(const float*, float*, const float*, const int
 using namespace rnnt;
 
 namespace {
-// Host memory (pageable or pinned) or device memory?  The one-call entry copies host costs behind its last kernel.
-bool is_device_pointer(const void* p) {
-    hipPointerAttribute_t attr;
-    const bool dev = hipPointerGetAttributes(&attr, p) == hipSuccess &&
-                     (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged);
-    (void)hipGetLastError();                       // (the query of a pageable pointer reports an error: not ours)
-    return dev;
-}
-
 rnntStatus_t dispatch(const void* acts, void* grads, const void* scale, const int* durations, int D, float sigma,
                       const int* labels, const int* label_lengths, const int* input_lengths, int A, int N, void* costs_dev,
                       void* costs_host, void* workspace, const rnntOptions& o, int dtype_code, int phases, bool want_grad) {

@@ -4,9 +4,6 @@
 // Every kernel is rnnt_tdt_kernels.h's; rnnt_host.h contributes only helpers (workspace alignment, the tuning constants,
 // the argument checks).
 #pragma once
-// (rnnt_host.h's stage-timer, marker and layout helpers are static and unused here: no profiling in this library)
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"
-#pragma clang diagnostic ignored "-Wunused-function"
 #include "rnnt_host.h"
 #include "rnnt_tdt_kernels.h"
 #include "../../include/rnnt_tdt.h"
@@ -86,13 +83,9 @@ static bool launch_tdt_grad(const typename Tag::store* acts, typename Tag::store
     const unsigned long long E = static_cast<unsigned long long>(N) * rps * W;
     const uintptr_t pa = reinterpret_cast<uintptr_t>(acts), pg = reinterpret_cast<uintptr_t>(grads);
     if (((pa | pg) & 15u) == 0) {
-        const unsigned long long cpk = 2 * 256;                        // packets per chunk (tdt_grad_kernel: PPT = 2)
-        const unsigned long long nchunks = (E / V + cpk - 1) / cpk;
-        const unsigned grid = static_cast<unsigned>(nchunks < static_cast<unsigned long long>(tune().gmax)
-                                                        ? (nchunks ? nchunks : 1) : tune().gmax);
-        const unsigned long long stride = static_cast<unsigned long long>(grid) * cpk * V;
-        hipLaunchKernelGGL((tdt_grad_kernel<Tag>), dim3(grid), dim3(256), 0, s, acts, grads, tab, grad_scale, E, W, A, RS,
-                           blank, rps, 1.0f / static_cast<float>(W), stride / W, static_cast<int>(stride % W));
+        const FlatGrid fg = flat_grid(E / V, 2, V);                    // (tdt_grad_kernel: PPT = 2)
+        hipLaunchKernelGGL((tdt_grad_kernel<Tag>), dim3(fg.grid), dim3(256), 0, s, acts, grads, tab, grad_scale, E, W, A, RS,
+                           blank, rps, 1.0f / static_cast<float>(W), fg.stride / W, static_cast<int>(fg.stride % W));
     } else {
         const unsigned long long blocks = (E + 255) / 256;
         const unsigned grid = static_cast<unsigned>(blocks < 65536 ? (blocks ? blocks : 1) : 65536);
@@ -163,14 +156,7 @@ rnntStatus_t run_tdt(const typename Tag::store* acts, typename Tag::store* grads
     }
     if (do_bwd && ok) ok = launch_tdt_grad<Tag>(acts, grads, tab, grad_scale, N, maxT, maxU, A, D, blank, s);
     if (!ok) return RNNT_STATUS_EXECUTION_FAILED;
-    if (costs_host != nullptr) {
-        if (hipMemcpyAsync(costs_host, costs_device, sizeof(C) * N, hipMemcpyDeviceToHost, s) != hipSuccess)
-            return RNNT_STATUS_MEMOPS_FAILED;
-        if (hipStreamSynchronize(s) != hipSuccess) return RNNT_STATUS_EXECUTION_FAILED;
-        for (int b = 0; b < N; ++b)
-            if (is_cost_invalid<C>(costs_host[b])) return RNNT_STATUS_INVALID_VALUE;
-    }
-    return RNNT_STATUS_SUCCESS;
+    return costs_host != nullptr ? finish_host_costs(costs_host, costs_device, N, s) : RNNT_STATUS_SUCCESS;
 }
 
 }  // namespace rnnt
