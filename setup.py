@@ -5,8 +5,8 @@
 
 The installed package is self-contained: warprnnt_pytorch/{*.py, _warp_rnnt_ext*.so, lib/libwarprnnt.so, include/rnnt.h}, and
 lib/libwarprnnt_pruned.so + include/rnnt_pruned.h for warprnnt_pytorch.pruned, lib/libwarprnnt_tdt.so + include/rnnt_tdt.h
-for warprnnt_pytorch.tdt and lib/libwarprnnt_hat.so + include/rnnt_hat.h for warprnnt_pytorch.hat when those libraries were
-built (or lie beside a WARP_RNNT_PATH library);
+for warprnnt_pytorch.tdt, lib/libwarprnnt_hat.so + include/rnnt_hat.h for warprnnt_pytorch.hat and lib/libwarprnnt_mblank.so +
+include/rnnt_mblank.h for warprnnt_pytorch.mblank when those libraries were built (or lie beside a WARP_RNNT_PATH library);
 no sys.path edits, no environment variables at run time (a WARP_RNNT_PATH naming ANOTHER library at run time is honoured by switching to
 the ctypes loader: the compiled module is linked to the library it was built with).
 torch must be importable at build time (--no-build-isolation), exactly as for the reference's setup.py, which imports it.
@@ -51,12 +51,13 @@ class build_native(build_py):
                 raise SystemExit("Could not find libwarprnnt.so in %s (WARP_RNNT_PATH)" % prebuilt)
         else:
             subprocess.run(["make", "-j3", "-C", os.path.join(ROOT, "warp-transducer_amd"), "lib/libwarprnnt.so",
-                            "lib/libwarprnnt_pruned.so", "lib/libwarprnnt_tdt.so", "lib/libwarprnnt_hat.so"], check=True)
+                            "lib/libwarprnnt_pruned.so", "lib/libwarprnnt_tdt.so", "lib/libwarprnnt_hat.so",
+                            "lib/libwarprnnt_mblank.so"], check=True)
             src = os.path.join(ROOT, "warp-transducer_amd", "lib", "libwarprnnt.so")
         shutil.copy2(src, os.path.join(lib_out, "libwarprnnt.so"))
-        # the pruned, TDT and HAT losses' libraries (warprnnt_pytorch.pruned / .tdt / .hat load them on first use): beside libwarprnnt.so when built or
+        # the pruned, TDT, HAT and multi-blank losses' libraries (warprnnt_pytorch.pruned / .tdt / .hat / .mblank load them on first use): beside libwarprnnt.so when built or
         # handed over; without it the package installs and everything else works
-        for extra in ("libwarprnnt_pruned.so", "libwarprnnt_tdt.so", "libwarprnnt_hat.so"):
+        for extra in ("libwarprnnt_pruned.so", "libwarprnnt_tdt.so", "libwarprnnt_hat.so", "libwarprnnt_mblank.so"):
             path = os.path.join(os.path.dirname(src), extra)
             if os.path.exists(path):
                 shutil.copy2(path, os.path.join(lib_out, extra))
@@ -66,6 +67,7 @@ class build_native(build_py):
         shutil.copy2(os.path.join(ROOT, "include", "rnnt_pruned.h"), os.path.join(inc_out, "rnnt_pruned.h"))
         shutil.copy2(os.path.join(ROOT, "include", "rnnt_tdt.h"), os.path.join(inc_out, "rnnt_tdt.h"))
         shutil.copy2(os.path.join(ROOT, "include", "rnnt_hat.h"), os.path.join(inc_out, "rnnt_hat.h"))
+        shutil.copy2(os.path.join(ROOT, "include", "rnnt_mblank.h"), os.path.join(inc_out, "rnnt_mblank.h"))
         spec = importlib.util.spec_from_file_location("_warprnnt_build_ext", os.path.join(PKG_SRC, "build_ext.py"))
         be = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(be)
@@ -75,7 +77,8 @@ class build_native(build_py):
 def _build_in_tree():
     if not os.environ.get("WARP_RNNT_PATH"):
         subprocess.run(["make", "-j3", "-C", os.path.join(ROOT, "warp-transducer_amd"), "lib/libwarprnnt.so",
-                        "lib/libwarprnnt_pruned.so", "lib/libwarprnnt_tdt.so", "lib/libwarprnnt_hat.so"], check=True)
+                        "lib/libwarprnnt_pruned.so", "lib/libwarprnnt_tdt.so", "lib/libwarprnnt_hat.so",
+                            "lib/libwarprnnt_mblank.so"], check=True)
     subprocess.run([sys.executable, os.path.join(PKG_SRC, "build_ext.py")], check=True)
 
 

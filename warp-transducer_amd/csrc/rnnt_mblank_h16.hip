@@ -1,0 +1,13 @@
+// rnnt_mblank_h16.hip -- the multi-blank loss for bf16 and fp16 storage (fp32 lattice), a code object of its own
+// (rnnt_mblank_impl.h says why).
+#define RNNT_MBLANK_INSTANTIATE_H16 1
+#include "rnnt_mblank_impl.h"
+
+namespace rnnt {
+template rnntStatus_t run_mblank<BF16>(const uint16_t*, uint16_t*, const float*, const int*, const int*, int, float,
+                                       const int*, const int*, const int*, int, int, float*, float*, void*,
+                                       const rnntOptions&, int, bool);
+template rnntStatus_t run_mblank<F16>(const uint16_t*, uint16_t*, const float*, const int*, const int*, int, float,
+                                      const int*, const int*, const int*, int, int, float*, float*, void*,
+                                      const rnntOptions&, int, bool);
+}  // namespace rnnt
