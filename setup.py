@@ -24,6 +24,10 @@ from setuptools.dist import Distribution
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 PKG_SRC = os.path.join(ROOT, "warp-transducer_amd", "warprnnt_pytorch")
+SIDE = ("pruned", "tdt", "hat", "mblank")          # warprnnt_pytorch.NAME loads lib/libwarprnnt_NAME.so (include/rnnt_NAME.h)
+SIDE_LIBS = ["libwarprnnt_%s.so" % name for name in SIDE]
+MAKE_LIBS = (["make", "-j3", "-C", os.path.join(ROOT, "warp-transducer_amd"), "lib/libwarprnnt.so"]
+             + ["lib/" + so for so in SIDE_LIBS])
 
 
 class BinaryDistribution(Distribution):
@@ -50,24 +54,19 @@ class build_native(build_py):
             if not os.path.exists(src):
                 raise SystemExit("Could not find libwarprnnt.so in %s (WARP_RNNT_PATH)" % prebuilt)
         else:
-            subprocess.run(["make", "-j3", "-C", os.path.join(ROOT, "warp-transducer_amd"), "lib/libwarprnnt.so",
-                            "lib/libwarprnnt_pruned.so", "lib/libwarprnnt_tdt.so", "lib/libwarprnnt_hat.so",
-                            "lib/libwarprnnt_mblank.so"], check=True)
+            subprocess.run(MAKE_LIBS, check=True)
             src = os.path.join(ROOT, "warp-transducer_amd", "lib", "libwarprnnt.so")
         shutil.copy2(src, os.path.join(lib_out, "libwarprnnt.so"))
-        # the pruned, TDT, HAT and multi-blank losses' libraries (warprnnt_pytorch.pruned / .tdt / .hat / .mblank load them on first use): beside libwarprnnt.so when built or
-        # handed over; without it the package installs and everything else works
-        for extra in ("libwarprnnt_pruned.so", "libwarprnnt_tdt.so", "libwarprnnt_hat.so", "libwarprnnt_mblank.so"):
+        # the side losses' libraries (their modules load them on first use): beside libwarprnnt.so when built or handed over;
+        # without one the package installs and everything else works
+        for extra in SIDE_LIBS:
             path = os.path.join(os.path.dirname(src), extra)
             if os.path.exists(path):
                 shutil.copy2(path, os.path.join(lib_out, extra))
         inc_out = os.path.join(pkg_out, "include")
         os.makedirs(inc_out, exist_ok=True)
-        shutil.copy2(os.path.join(ROOT, "include", "rnnt.h"), os.path.join(inc_out, "rnnt.h"))
-        shutil.copy2(os.path.join(ROOT, "include", "rnnt_pruned.h"), os.path.join(inc_out, "rnnt_pruned.h"))
-        shutil.copy2(os.path.join(ROOT, "include", "rnnt_tdt.h"), os.path.join(inc_out, "rnnt_tdt.h"))
-        shutil.copy2(os.path.join(ROOT, "include", "rnnt_hat.h"), os.path.join(inc_out, "rnnt_hat.h"))
-        shutil.copy2(os.path.join(ROOT, "include", "rnnt_mblank.h"), os.path.join(inc_out, "rnnt_mblank.h"))
+        for header in ["rnnt.h"] + ["rnnt_%s.h" % name for name in SIDE]:
+            shutil.copy2(os.path.join(ROOT, "include", header), os.path.join(inc_out, header))
         spec = importlib.util.spec_from_file_location("_warprnnt_build_ext", os.path.join(PKG_SRC, "build_ext.py"))
         be = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(be)
@@ -76,9 +75,7 @@ class build_native(build_py):
 
 def _build_in_tree():
     if not os.environ.get("WARP_RNNT_PATH"):
-        subprocess.run(["make", "-j3", "-C", os.path.join(ROOT, "warp-transducer_amd"), "lib/libwarprnnt.so",
-                        "lib/libwarprnnt_pruned.so", "lib/libwarprnnt_tdt.so", "lib/libwarprnnt_hat.so",
-                            "lib/libwarprnnt_mblank.so"], check=True)
+        subprocess.run(MAKE_LIBS, check=True)
     subprocess.run([sys.executable, os.path.join(PKG_SRC, "build_ext.py")], check=True)
 
 

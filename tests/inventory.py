@@ -72,6 +72,45 @@ def declared(header):
     return set(re.findall(r"^rnntStatus_t\s+(\w+)\(", open(os.path.join(ROOT, "include", header)).read(), re.M))
 
 
+def declared_signatures(header):
+    """{function: [kind of each parameter]} of the functions a header of include/ declares, in the kinds a ctypes table has to
+    tell apart: 'pointer', 'size_t*', 'int', 'float', 'rnntOptions'.  A parameter of any other type is an error."""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+    out = {}
+    for name, params in re.findall(r"^rnntStatus_t\s+(\w+)\(([^()]*)\)\s*;", text, re.M):
+        kinds = []
+        for p in params.split(","):
+            ctype = re.sub(r"\bconst\b|\w+\s*$|\s", "", p)                              # the type without the parameter's name
+            if ctype.endswith("*"):
+                kinds.append("size_t*" if ctype == "size_t*" else "pointer")
+            elif ctype in ("int", "float", "rnntOptions"):
+                kinds.append(ctype)
+            else:
+                raise ValueError("%s: %s(... %s ...): a parameter type this parser does not know" % (header, name, p.strip()))
+        out[name] = kinds
+    return out
+
+
+def binding_faults(exports, header):
+    """Where a ctypes table {name: (restype, argtypes)} departs from the header's declarations: names, restype c_int, the
+    number of arguments and the kind of each, position by position.  [] when it matches."""
+    import ctypes as C
+    from warprnnt_pytorch import _lib
+    ctype = {"pointer": C.c_void_p, "size_t*": C.POINTER(C.c_size_t), "int": C.c_int, "float": C.c_float,
+             "rnntOptions": _lib.rnntOptions}
+    want = declared_signatures(header)
+    faults = ["%s: only in %s" % (n, "the table" if n in exports else header) for n in sorted(set(exports) ^ set(want))]
+    for name in sorted(set(exports) & set(want)):
+        res, args = exports[name]
+        if res is not C.c_int:
+            faults.append("%s: restype %r" % (name, res))
+        if len(args) != len(want[name]):
+            faults.append("%s: %d arguments, %s declares %d" % (name, len(args), header, len(want[name])))
+        faults += ["%s: argument %d is %r, %s declares %s" % (name, i, a, header, k)
+                   for i, (a, k) in enumerate(zip(args, want[name])) if a is not ctype[k]]
+    return faults
+
+
 def side_inventory(lib):
     """{f32 | f64 | h16: kernel names} of a side library's three code objects, each recognised by its store tag."""
     readelf, cxxfilt = _tool("llvm-readelf"), _tool("llvm-cxxfilt") or shutil.which("c++filt")

@@ -71,11 +71,6 @@ def test_exports_equal_the_header():
     assert declared and exported == declared, (sorted(exported), sorted(declared))
 
 
-def test_python_bindings_match_the_header():
-    from warprnnt_pytorch import tdt
-    assert set(tdt.EXPORTS) == I.declared(HEADER)
-
-
 def test_python_refuses_bad_durations():
     from warprnnt_pytorch import tdt
     for d in ((), (1, 1), (2, 1), (-1, 1), (0,), (0, 65), tuple(range(9))):
