@@ -22,7 +22,7 @@ def stage_of(name):
 
 
 def stats_group(row_bytes):
-    """launch_hat_stats: lanes per row."""
+    """launch_hat_stats (stats_grid, csrc/rnnt_side_host.h, with HAT's 4096-byte threshold): lanes per row."""
     return 4 if row_bytes <= 256 else 16 if row_bytes <= 4096 else 64
 
 

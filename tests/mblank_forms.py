@@ -21,7 +21,7 @@ def stage_of(name):
 
 
 def stats_group(row_bytes):
-    """launch_mblank_stats: lanes per row."""
+    """launch_mblank_stats (stats_grid, csrc/rnnt_side_host.h): lanes per row."""
     return 4 if row_bytes <= 256 else 16 if row_bytes <= 2048 else 64
 
 

@@ -20,7 +20,7 @@ def stage_of(name):
 
 
 def stats_group(row_bytes):
-    """launch_tdt_stats: lanes per row (row_bytes: the token columns only)."""
+    """launch_tdt_stats (stats_grid, csrc/rnnt_side_host.h): lanes per row (row_bytes: the token columns only)."""
     return 4 if row_bytes <= 256 else 16 if row_bytes <= 2048 else 64
 
 

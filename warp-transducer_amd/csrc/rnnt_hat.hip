@@ -4,40 +4,10 @@
 #include "rnnt_hat_impl.h"
 
 namespace rnnt {
-template rnntStatus_t run_hat<F32>(const float*, float*, const float*, const int*, const int*, const int*, int, int, float*,
-                                   float*, void*, const rnntOptions&, int, bool);
+template rnntStatus_t run_hat<F32>(const SideCall&);
 }  // namespace rnnt
 
 using namespace rnnt;
-
-namespace {
-rnntStatus_t dispatch(const void* acts, void* grads, const void* scale, const int* labels, const int* label_lengths,
-                      const int* input_lengths, int A, int N, void* costs_dev, void* costs_host, void* workspace,
-                      const rnntOptions& o, int dtype_code, int phases, bool want_grad) {
-    switch (dtype_code) {
-        case 0:
-            return run_hat<F32>(static_cast<const float*>(acts), static_cast<float*>(grads), static_cast<const float*>(scale),
-                                labels, label_lengths, input_lengths, A, N, static_cast<float*>(costs_dev),
-                                static_cast<float*>(costs_host), workspace, o, phases, want_grad);
-        case 1:
-            return run_hat<F64>(static_cast<const double*>(acts), static_cast<double*>(grads),
-                                static_cast<const double*>(scale), labels, label_lengths, input_lengths, A, N,
-                                static_cast<double*>(costs_dev), static_cast<double*>(costs_host), workspace, o, phases,
-                                want_grad);
-        case 2:
-            return run_hat<BF16>(static_cast<const uint16_t*>(acts), static_cast<uint16_t*>(grads),
-                                 static_cast<const float*>(scale), labels, label_lengths, input_lengths, A, N,
-                                 static_cast<float*>(costs_dev), static_cast<float*>(costs_host), workspace, o, phases,
-                                 want_grad);
-        case 3:
-            return run_hat<F16>(static_cast<const uint16_t*>(acts), static_cast<uint16_t*>(grads),
-                                static_cast<const float*>(scale), labels, label_lengths, input_lengths, A, N,
-                                static_cast<float*>(costs_dev), static_cast<float*>(costs_host), workspace, o, phases,
-                                want_grad);
-        default: return RNNT_STATUS_INVALID_VALUE;
-    }
-}
-}  // namespace
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -53,31 +23,29 @@ rnntStatus_t get_workspace_size_hat(int maxT, int maxU, int minibatch, int dtype
 rnntStatus_t compute_hat_loss(const void* activations, void* gradients, const int* flat_labels, const int* label_lengths,
                               const int* input_lengths, int alphabet_size, int minibatch, void* costs, void* workspace,
                               rnntOptions options, int dtype_code) {
-    if (bad_args(activations, flat_labels, label_lengths, input_lengths, costs, workspace, alphabet_size, minibatch,
-                 options) || loc_of(options) != RNNT_GPU)
+    SideCall c;
+    if (side_entry_loss(c, activations, gradients, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch, costs,
+                        workspace, options))
         return RNNT_STATUS_INVALID_VALUE;
-    const bool dev = is_device_pointer(costs);
-    return dispatch(activations, gradients, nullptr, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch,
-                    dev ? costs : nullptr, dev ? nullptr : costs, workspace, options, dtype_code, 3, gradients != nullptr);
+    return side_dispatch(dtype_code, [&](auto tag) { return run_hat<decltype(tag)>(c); });
 }
 
 rnntStatus_t compute_hat_loss_fwd(const void* activations, const int* flat_labels, const int* label_lengths,
                                   const int* input_lengths, int alphabet_size, int minibatch, void* costs_device,
                                   void* workspace, rnntOptions options, int dtype_code, int prepare_backward) {
-    if (bad_args(activations, flat_labels, label_lengths, input_lengths, costs_device, workspace, alphabet_size, minibatch,
-                 options) || loc_of(options) != RNNT_GPU)
+    SideCall c;
+    if (side_entry_fwd(c, activations, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch, costs_device,
+                       workspace, options, prepare_backward))
         return RNNT_STATUS_INVALID_VALUE;
-    return dispatch(activations, nullptr, nullptr, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch,
-                    costs_device, nullptr, workspace, options, dtype_code, 1, prepare_backward != 0);
+    return side_dispatch(dtype_code, [&](auto tag) { return run_hat<decltype(tag)>(c); });
 }
 
 rnntStatus_t compute_hat_loss_bwd(const void* activations, void* gradients, const void* grad_scale_device,
                                   int alphabet_size, int minibatch, void* workspace, rnntOptions options, int dtype_code) {
-    if (activations == nullptr || gradients == nullptr || workspace == nullptr || alphabet_size <= 0 || minibatch <= 0 ||
-        options.maxT <= 0 || options.maxU <= 0 || loc_of(options) != RNNT_GPU)
+    SideCall c;
+    if (side_entry_bwd(c, activations, gradients, grad_scale_device, alphabet_size, minibatch, workspace, options))
         return RNNT_STATUS_INVALID_VALUE;
-    return dispatch(activations, gradients, grad_scale_device, nullptr, nullptr, nullptr, alphabet_size, minibatch, nullptr,
-                    nullptr, workspace, options, dtype_code, 2, true);
+    return side_dispatch(dtype_code, [&](auto tag) { return run_hat<decltype(tag)>(c); });
 }
 
 }  // extern "C"

@@ -4,8 +4,6 @@
 #include "rnnt_hat_impl.h"
 
 namespace rnnt {
-template rnntStatus_t run_hat<BF16>(const uint16_t*, uint16_t*, const float*, const int*, const int*, const int*, int, int,
-                                    float*, float*, void*, const rnntOptions&, int, bool);
-template rnntStatus_t run_hat<F16>(const uint16_t*, uint16_t*, const float*, const int*, const int*, const int*, int, int,
-                                   float*, float*, void*, const rnntOptions&, int, bool);
+template rnntStatus_t run_hat<BF16>(const SideCall&);
+template rnntStatus_t run_hat<F16>(const SideCall&);
 }  // namespace rnnt

@@ -1,4 +1,5 @@
-// rnnt_host.h -- what the host translation units of the main library and of the side libraries (pruned, TDT, HAT) share:
+// rnnt_host.h -- what the host translation units of the main library and of the side libraries (pruned, TDT, HAT, multi-blank;
+// what only those four share is rnnt_side_host.h's) share:
 // workspace layout, tuning constants, the launch plan, the launchers of the two stages every lattice path runs (lattice,
 // coefficients), and the small host helpers of the drivers (flat_grid, finish_host_costs, is_device_pointer, bad_args).
 //   rnnt_gpu.hip    the materialised path (row statistics ... gradient stream) and the C entry points of rnnt.h

@@ -4,7 +4,5 @@
 #include "rnnt_mblank_impl.h"
 
 namespace rnnt {
-template rnntStatus_t run_mblank<F64>(const double*, double*, const double*, const int*, const int*, int, float, const int*,
-                                      const int*, const int*, int, int, double*, double*, void*, const rnntOptions&, int,
-                                      bool);
+template rnntStatus_t run_mblank<F64>(const SideCall&, const int*, const int*, int, float);
 }  // namespace rnnt

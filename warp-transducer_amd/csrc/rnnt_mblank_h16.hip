@@ -4,10 +4,6 @@
 #include "rnnt_mblank_impl.h"
 
 namespace rnnt {
-template rnntStatus_t run_mblank<BF16>(const uint16_t*, uint16_t*, const float*, const int*, const int*, int, float,
-                                       const int*, const int*, const int*, int, int, float*, float*, void*,
-                                       const rnntOptions&, int, bool);
-template rnntStatus_t run_mblank<F16>(const uint16_t*, uint16_t*, const float*, const int*, const int*, int, float,
-                                      const int*, const int*, const int*, int, int, float*, float*, void*,
-                                      const rnntOptions&, int, bool);
+template rnntStatus_t run_mblank<BF16>(const SideCall&, const int*, const int*, int, float);
+template rnntStatus_t run_mblank<F16>(const SideCall&, const int*, const int*, int, float);
 }  // namespace rnnt

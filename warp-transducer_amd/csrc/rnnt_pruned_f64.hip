@@ -4,6 +4,5 @@
 #include "rnnt_pruned_impl.h"
 
 namespace rnnt {
-template rnntStatus_t run_pruned<F64>(const double*, double*, const double*, const int*, int, const int*, const int*,
-                                      const int*, int, int, double*, double*, void*, const rnntOptions&, int, bool);
+template rnntStatus_t run_pruned<F64>(const SideCall&, const int*, int);
 }  // namespace rnnt

@@ -4,12 +4,8 @@
 #include "rnnt_pruned_impl.h"
 
 namespace rnnt {
-template rnntStatus_t run_pruned<BF16>(const uint16_t*, uint16_t*, const float*, const int*, int, const int*, const int*,
-                                       const int*, int, int, float*, float*, void*, const rnntOptions&, int, bool);
-template rnntStatus_t run_pruned<F16>(const uint16_t*, uint16_t*, const float*, const int*, int, const int*, const int*,
-                                      const int*, int, int, float*, float*, void*, const rnntOptions&, int, bool);
-template rnntStatus_t run_prune_ranges<BF16>(const uint16_t*, const uint16_t*, const int*, const int*, const int*, int, int,
-                                             int, int*, void*, const rnntOptions&);
-template rnntStatus_t run_prune_ranges<F16>(const uint16_t*, const uint16_t*, const int*, const int*, const int*, int, int,
-                                            int, int*, void*, const rnntOptions&);
+template rnntStatus_t run_pruned<BF16>(const SideCall&, const int*, int);
+template rnntStatus_t run_pruned<F16>(const SideCall&, const int*, int);
+template rnntStatus_t run_prune_ranges<BF16>(const SideCall&, const void*, int, int*);
+template rnntStatus_t run_prune_ranges<F16>(const SideCall&, const void*, int, int*);
 }  // namespace rnnt

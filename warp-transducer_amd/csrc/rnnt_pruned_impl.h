@@ -4,8 +4,9 @@
 //     rnnt_pruned.hip   F32 (+ every C entry point)     rnnt_pruned_f64.hip   F64     rnnt_pruned_h16.hip   BF16, F16
 // The lattice, the coefficient stage and the additive joint's partition stage are the launchers of rnnt_host.h /
 // rnnt_joint_impl.h, unchanged; the two streaming stages of the pruned loss and the ranges kernels are rnnt_pruned_kernels.h.
+// The call record, its buffer checks and the launch arithmetic are rnnt_side_host.h's.
 #pragma once
-#include "rnnt_host.h"
+#include "rnnt_side_host.h"
 #include "rnnt_joint_impl.h"
 #include "rnnt_pruned_kernels.h"
 #include "../../include/rnnt_pruned.h"
@@ -26,19 +27,16 @@ static inline PrunedLayout pruned_layout(int maxT, int maxU, int N, size_t lat) 
     return pl;
 }
 
-// Stage 1 of the pruned loss: G lanes per row, the smallest group that keeps a lane's share of the row's packets at a few rounds
+// Stage 1 of the pruned loss: G lanes per row (stats_grid)
 template <typename Tag>
 static void launch_pruned_stats(Plan<typename Tag::comp>& p, const typename Tag::store* acts, const int2* win, int S) {
-    const size_t row_bytes = static_cast<size_t>(p.A) * sizeof(typename Tag::store);
-    const int G = row_bytes <= 256 ? 4 : row_bytes <= 2048 ? 16 : 64;
-    const long long rows = static_cast<long long>(p.maxT) * S;
-    const unsigned gx = static_cast<unsigned>((rows * G + 255) / 256);
+    const StatsGrid sg = stats_grid(static_cast<size_t>(p.A) * sizeof(typename Tag::store), static_cast<long long>(p.maxT) * S);
     for (int b0 = 0; b0 < p.N; b0 += kGridSamples) {
-        const dim3 grid(gx, p.N - b0 < kGridSamples ? p.N - b0 : kGridSamples);
+        const dim3 grid(sg.gx, grid_samples(p.N, b0));
 #define RNNT_PSTATS(GG)                                                                                              \
         hipLaunchKernelGGL((pruned_stats_kernel<Tag, GG>), grid, dim3(256), 0, p.stream, acts, win, p.labels,        \
                            p.label_lengths, p.lp2, p.logz, p.maxT, p.maxU, p.Up, S, p.A, p.blank, b0, p.poison)
-        if (G == 4) RNNT_PSTATS(4); else if (G == 16) RNNT_PSTATS(16); else RNNT_PSTATS(64);
+        if (sg.G == 4) RNNT_PSTATS(4); else if (sg.G == 16) RNNT_PSTATS(16); else RNNT_PSTATS(64);
 #undef RNNT_PSTATS
     }
     p.check();
@@ -51,77 +49,71 @@ static void launch_pruned_grad(Plan<typename Tag::comp>& p, const typename Tag::
     constexpr int V = Vec<Tag>::N;
     const unsigned long long R = static_cast<unsigned long long>(p.N) * p.maxT * S;
     const unsigned long long E = R * p.A;
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(acts), pg = reinterpret_cast<uintptr_t>(grads);
-    if (((pa | pg) & 15u) == 0 && p.A <= (1 << 23)) {
+    if (packets_aligned(acts, grads) && p.A <= (1 << 23)) {
         const FlatGrid fg = flat_grid(E / V, 2, V);                    // (pruned_grad_kernel: PPT = 2)
         hipLaunchKernelGGL((pruned_grad_kernel<Tag>), dim3(fg.grid), dim3(256), 0, p.stream, acts, grads, p.rowtab, win,
                            grad_scale, E, p.A, p.blank, S, p.maxT, p.maxU, 1.0f / static_cast<float>(p.A), fg.stride / p.A,
                            static_cast<int>(fg.stride % p.A));
     } else {
-        const unsigned long long blocks = (E + 255) / 256;
-        const unsigned grid = static_cast<unsigned>(blocks < 65536 ? (blocks ? blocks : 1) : 65536);
-        hipLaunchKernelGGL((pruned_grad_elem_kernel<Tag>), dim3(grid), dim3(256), 0, p.stream, acts, grads, p.rowtab, win,
-                           grad_scale, E, p.A, p.blank, S, p.maxT, p.maxU);
+        hipLaunchKernelGGL((pruned_grad_elem_kernel<Tag>), dim3(elem_grid(E)), dim3(256), 0, p.stream, acts, grads, p.rowtab,
+                           win, grad_scale, E, p.A, p.blank, S, p.maxT, p.maxU);
     }
     p.check();
 }
 
-// The pruned loss.  phases: bit 0 = forward (windows, statistics, lattice, and with want_grad the coefficient table), bit 1 =
-// gradient stream from the workspace a forward call left.  costs_host != nullptr: the one-call entry with costs in host memory
-// (copied behind the last kernel, the stream synchronised, the cost markers answered with RNNT_STATUS_INVALID_VALUE).
+// The pruned loss of call `c` (SideCall: phases, host or device costs) over windows of S label positions per frame.
 template <typename Tag>
-rnntStatus_t run_pruned(const typename Tag::store* acts, typename Tag::store* grads, const typename Tag::comp* grad_scale,
-                        const int* ranges, int S, const int* labels, const int* label_lengths, const int* input_lengths,
-                        int A, int N, typename Tag::comp* costs_device, typename Tag::comp* costs_host, void* workspace,
-                        const rnntOptions& opt, int phases, bool want_grad) {
+rnntStatus_t run_pruned(const SideCall& c, const int* ranges, int S) {
     using St = typename Tag::store;
     using C = typename Tag::comp;
+    const St* acts = static_cast<const St*>(c.acts);
+    St* grads = static_cast<St*>(c.grads);
+    const int N = c.N;
     Plan<C> p;
-    if (!make_plan(p, A, N, opt, workspace, labels, label_lengths, input_lengths, costs_device, /*joint=*/true))
+    if (!make_plan(p, c.A, N, c.opt, c.workspace, c.labels, c.label_lengths, c.input_lengths, static_cast<C*>(c.costs_dev),
+                   /*joint=*/true))
         return RNNT_STATUS_INVALID_VALUE;
     if (S < 1 || S > p.maxU) return RNNT_STATUS_INVALID_VALUE;
     // the gradient stream decodes rows in 32-bit arithmetic; the statistics kernel counts a sample's rows in an int
     const unsigned long long R = static_cast<unsigned long long>(N) * p.maxT * S;
     if (R >= (1ull << 32) || static_cast<long long>(p.maxT) * S * 64 >= 0x7fffffffLL) return RNNT_STATUS_INVALID_VALUE;
-    const bool do_fwd = (phases & 1) != 0, do_bwd = (phases & 2) != 0 && want_grad;
-    if (do_bwd && grads == nullptr) return RNNT_STATUS_INVALID_VALUE;
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(acts), pg = reinterpret_cast<uintptr_t>(grads);
-    if (pa % sizeof(St) != 0 || (grads != nullptr && pg % sizeof(St) != 0)) return RNNT_STATUS_INVALID_VALUE;
-    if (do_bwd && pg != pa) {                          // in place, or not overlapping at all
-        const unsigned long long bytes = R * static_cast<unsigned long long>(A) * sizeof(St);
-        if ((pg > pa ? pg - pa : pa - pg) < bytes) return RNNT_STATUS_INVALID_VALUE;
-    }
+    bool do_fwd, do_bwd;
+    if (!side_buffers_ok(c, sizeof(St), R * c.A, do_fwd, do_bwd)) return RNNT_STATUS_INVALID_VALUE;
     const PrunedLayout pl = pruned_layout(p.maxT, p.maxU, N, sizeof(C));
-    char* ws = reinterpret_cast<char*>(align_up(reinterpret_cast<size_t>(workspace)));
+    char* ws = reinterpret_cast<char*>(align_up(reinterpret_cast<size_t>(c.workspace)));
     int2* win = reinterpret_cast<int2*>(ws + pl.win);
     int* bad = reinterpret_cast<int*>(ws + pl.bad);
 
     if (do_fwd) {
         for (int b0 = 0; b0 < N; b0 += kGridSamples)
-            hipLaunchKernelGGL((pruned_prep_kernel<C>), dim3((p.maxT + 31) / 32, N - b0 < kGridSamples ? N - b0 : kGridSamples),
-                               dim3(256), 0, p.stream, ranges, input_lengths, label_lengths, p.lp2, p.logz, win, bad, p.maxT,
-                               p.maxU, p.Up, S, b0);
+            hipLaunchKernelGGL((pruned_prep_kernel<C>), dim3((p.maxT + 31) / 32, grid_samples(N, b0)), dim3(256), 0, p.stream,
+                               ranges, c.input_lengths, c.label_lengths, p.lp2, p.logz, win, bad, p.maxT, p.maxU, p.Up, S, b0);
         p.check();
         launch_pruned_stats<Tag>(p, acts, win, S);
-        launch_lattice(p, want_grad);
+        launch_lattice(p, c.want_grad);
         hipLaunchKernelGGL((pruned_fix_kernel<C>), dim3((N + 255) / 256), dim3(256), 0, p.stream, bad, p.costs_dev, N);
         p.check();
-        if (want_grad) launch_coef(p);
+        if (c.want_grad) launch_coef(p);
     }
-    if (do_bwd) launch_pruned_grad<Tag>(p, acts, grads, grad_scale, win, S);
+    if (do_bwd) launch_pruned_grad<Tag>(p, acts, grads, static_cast<const C*>(c.grad_scale), win, S);
     if (p.failed) return RNNT_STATUS_EXECUTION_FAILED;
-    return costs_host != nullptr ? finish_host_costs(costs_host, p.costs_dev, N, p.stream) : RNNT_STATUS_SUCCESS;
+    return c.costs_host != nullptr ? finish_host_costs(static_cast<C*>(c.costs_host), p.costs_dev, N, p.stream)
+                                   : RNNT_STATUS_SUCCESS;
 }
 
 // Prune ranges of the additive joint: its partition stage (row maxima, Z: lp2 / log Z of every cell), the lattice in both
 // directions, then the window sums of the occupancy and the per-sample repair.  No coefficient stage: the record table
-// overlays nothing.  Enqueue only.
+// overlays nothing.  Enqueue only.  Of `c` it reads the transcription activations (acts), the labels and lengths, A, N, the
+// workspace and the options.
 template <typename Tag>
-rnntStatus_t run_prune_ranges(const typename Tag::store* f, const typename Tag::store* g, const int* labels,
-                              const int* label_lengths, const int* input_lengths, int A, int N, int S, int* ranges,
-                              void* workspace, const rnntOptions& opt) {
+rnntStatus_t run_prune_ranges(const SideCall& c, const void* pred_acts, int S, int* ranges) {
+    const typename Tag::store* f = static_cast<const typename Tag::store*>(c.acts);
+    const typename Tag::store* g = static_cast<const typename Tag::store*>(pred_acts);
+    const int *label_lengths = c.label_lengths, *input_lengths = c.input_lengths;
+    const int A = c.A, N = c.N;
     Plan<float> p;
-    if (!make_plan(p, A, N, opt, workspace, labels, label_lengths, input_lengths, static_cast<float*>(nullptr), /*joint=*/true))
+    if (!make_plan(p, A, N, c.opt, c.workspace, c.labels, label_lengths, input_lengths, static_cast<float*>(nullptr),
+                   /*joint=*/true))
         return RNNT_STATUS_INVALID_VALUE;
     if (S < 2 || S > p.maxU) return RNNT_STATUS_INVALID_VALUE;
     // (the partition stage's addressing limits, as run_gpu_joint checks them)
@@ -132,37 +124,26 @@ rnntStatus_t run_prune_ranges(const typename Tag::store* f, const typename Tag::
     launch_lattice(p, /*with_beta=*/true);
     const size_t lds = static_cast<size_t>(4) * p.maxU * sizeof(double);
     for (int b0 = 0; b0 < N; b0 += kGridSamples)
-        hipLaunchKernelGGL(pruned_window_kernel<0>, dim3((p.maxT + 3) / 4, N - b0 < kGridSamples ? N - b0 : kGridSamples),
-                           dim3(256), lds, p.stream, p.alpha, p.beta, p.offa, p.offb, p.llf, input_lengths, label_lengths,
-                           ranges, p.maxT, p.maxU, p.Up, S, p.lat_w, p.lat_sh, b0);
+        hipLaunchKernelGGL(pruned_window_kernel<0>, dim3((p.maxT + 3) / 4, grid_samples(N, b0)), dim3(256), lds, p.stream,
+                           p.alpha, p.beta, p.offa, p.offb, p.llf, input_lengths, label_lengths, ranges, p.maxT, p.maxU, p.Up, S, p.lat_w, p.lat_sh, b0);
     hipLaunchKernelGGL(pruned_ranges_kernel<0>, dim3((N + 63) / 64), dim3(64), 0, p.stream, input_lengths, label_lengths, ranges,
                        N, p.maxT, p.maxU, S);
     p.check();
     return p.failed ? RNNT_STATUS_EXECUTION_FAILED : RNNT_STATUS_SUCCESS;
 }
 
-}  // namespace rnnt
-
-namespace rnnt {
-#define RNNT_PRUNED_DECLARE(TAG, ST, CT)                                                                                  \
-    extern template rnntStatus_t run_pruned<TAG>(const ST*, ST*, const CT*, const int*, int, const int*, const int*,      \
-                                                 const int*, int, int, CT*, CT*, void*, const rnntOptions&, int, bool);
-#define RNNT_RANGES_DECLARE(TAG, ST)                                                                                      \
-    extern template rnntStatus_t run_prune_ranges<TAG>(const ST*, const ST*, const int*, const int*, const int*, int, int, \
-                                                       int, int*, void*, const rnntOptions&);
 #ifndef RNNT_PRUNED_INSTANTIATE_F32
-RNNT_PRUNED_DECLARE(F32, float, float)
-RNNT_RANGES_DECLARE(F32, float)
+extern template rnntStatus_t run_pruned<F32>(const SideCall&, const int*, int);
+extern template rnntStatus_t run_prune_ranges<F32>(const SideCall&, const void*, int, int*);
 #endif
 #ifndef RNNT_PRUNED_INSTANTIATE_F64
-RNNT_PRUNED_DECLARE(F64, double, double)
+extern template rnntStatus_t run_pruned<F64>(const SideCall&, const int*, int);
 #endif
 #ifndef RNNT_PRUNED_INSTANTIATE_H16
-RNNT_PRUNED_DECLARE(BF16, uint16_t, float)
-RNNT_PRUNED_DECLARE(F16, uint16_t, float)
-RNNT_RANGES_DECLARE(BF16, uint16_t)
-RNNT_RANGES_DECLARE(F16, uint16_t)
+extern template rnntStatus_t run_pruned<BF16>(const SideCall&, const int*, int);
+extern template rnntStatus_t run_pruned<F16>(const SideCall&, const int*, int);
+extern template rnntStatus_t run_prune_ranges<BF16>(const SideCall&, const void*, int, int*);
+extern template rnntStatus_t run_prune_ranges<F16>(const SideCall&, const void*, int, int*);
 #endif
-#undef RNNT_PRUNED_DECLARE
-#undef RNNT_RANGES_DECLARE
+
 }  // namespace rnnt

@@ -4,6 +4,5 @@
 #include "rnnt_tdt_impl.h"
 
 namespace rnnt {
-template rnntStatus_t run_tdt<F64>(const double*, double*, const double*, const int*, int, float, const int*, const int*,
-                                   const int*, int, int, double*, double*, void*, const rnntOptions&, int, bool);
+template rnntStatus_t run_tdt<F64>(const SideCall&, const int*, int, float);
 }  // namespace rnnt

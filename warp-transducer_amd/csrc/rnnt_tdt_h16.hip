@@ -4,8 +4,6 @@
 #include "rnnt_tdt_impl.h"
 
 namespace rnnt {
-template rnntStatus_t run_tdt<BF16>(const uint16_t*, uint16_t*, const float*, const int*, int, float, const int*,
-                                    const int*, const int*, int, int, float*, float*, void*, const rnntOptions&, int, bool);
-template rnntStatus_t run_tdt<F16>(const uint16_t*, uint16_t*, const float*, const int*, int, float, const int*, const int*,
-                                   const int*, int, int, float*, float*, void*, const rnntOptions&, int, bool);
+template rnntStatus_t run_tdt<BF16>(const SideCall&, const int*, int, float);
+template rnntStatus_t run_tdt<F16>(const SideCall&, const int*, int, float);
 }  // namespace rnnt
