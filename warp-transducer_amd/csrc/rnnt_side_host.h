@@ -1,8 +1,9 @@
-// rnnt_side_host.h -- what the host drivers of the four side libraries (pruned, TDT, HAT, multi-blank) share on top of
-// rnnt_host.h: the call record their C entry points fill (SideCall), the dtype switch (side_dispatch), the buffer checks
-// of every run_X (side_buffers_ok), the cell-table workspace of TDT and multi-blank, and the launch arithmetic of the
-// statistics and gradient launchers.  Host code only: no kernel is named here, so a library's code objects hold exactly
-// the kernels its own rnnt_X_impl.h launches.
+// rnnt_side_host.h -- what the host drivers of the side libraries share on top of rnnt_host.h (the four losses -- pruned,
+// TDT, HAT, multi-blank -- all of it; the TDT alignment the dtype switch, the cell table and the launch arithmetic): the
+// call record their C entry points fill (SideCall), the dtype switch (side_dispatch), the buffer checks of every run_X
+// (side_buffers_ok), the cell-table workspace of TDT and multi-blank, and the launch arithmetic of the statistics and
+// gradient launchers.  Host code only: no kernel is named here, so a library's code objects hold exactly the kernels its
+// own rnnt_X_impl.h launches.
 #pragma once
 #include "rnnt_host.h"
 

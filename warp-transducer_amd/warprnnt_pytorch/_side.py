@@ -1,5 +1,6 @@
-"""What the side-loss modules (pruned, tdt, hat, mblank) share: the loader of a side library, its workspace-size cache, the
-checks of (logits, labels, act_lens, label_lens) and the skeleton of the two-phase autograd function.
+"""What the side modules (the losses pruned, tdt, hat, mblank, and tdt_align) share: the loader of a side library, its
+workspace-size cache, the checks of (logits, labels, act_lens, label_lens) and, for the losses, the skeleton of the two-phase
+autograd function.
 
 Each side library is a separate shared object next to libwarprnnt.so, loaded on the first call (`import warprnnt_pytorch` does
 not need it); a missing library is an error, there is no fallback.  The ctypes table (`EXPORTS`), the checks of its own

@@ -43,9 +43,10 @@ def durations_array(durations):
     return (C.c_int * len(d))(*d)
 
 
-def _certify(logits, labels, act_lens, label_lens, D, blank, validate):
+def _certify(logits, labels, act_lens, label_lens, D, blank, validate, what="the TDT loss"):
+    """The checks of TDT logits (N, T, U, A + D) -> A; `what` names the entry in the GPU-only refusal (tdt_align.py's too)."""
     _side.certify(logits, labels, act_lens, label_lens, validate,
-                  "the TDT loss runs on the GPU only: logits are on %(device)s")
+                  what + " runs on the GPU only: logits are on %(device)s")
     if logits.shape[2] != labels.shape[1] + 1:
         raise ValueError("logits.shape[2] must be labels.shape[1] + 1")
     A = logits.shape[3] - D
