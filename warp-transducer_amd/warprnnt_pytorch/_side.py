@@ -98,9 +98,10 @@ def _cost_dtype(logits):
     return torch.float64 if logits.dtype == torch.float64 else torch.float32
 
 
-def forward(ctx, logits, labels, workspace_size, reduction, call, what):
+def forward(ctx, logits, labels, workspace_size, reduction, call, what, also_save=()):
     """The forward half of a two-phase loss.  call(costs, labels, workspace, prepare_backward) -> status makes the loss's
-    *_fwd call (named `what`) on these device pointers.  Leaves the logits, the workspace and mean_scale in ctx."""
+    *_fwd call (named `what`) on these device pointers.  Leaves the logits, the workspace and mean_scale in ctx; `also_save`:
+    further tensors the backward half needs (ctx.saved_tensors holds them behind the logits)."""
     B, dev = logits.shape[0], logits.device
     need_grad = logits.requires_grad
     with torch.cuda.device(dev):
@@ -108,7 +109,7 @@ def forward(ctx, logits, labels, workspace_size, reduction, call, what):
         ws = torch.empty(workspace_size, dtype=torch.uint8, device=dev)
         lab_ptr = labels.data_ptr() if labels.numel() else costs.data_ptr()    # maxU == 1: never read
         _lib.check(call(costs.data_ptr(), lab_ptr, ws.data_ptr(), 1 if need_grad else 0), what)
-    ctx.save_for_backward(logits)
+    ctx.save_for_backward(logits, *also_save)
     ctx.workspace = ws if need_grad else None
     ctx.mean_scale = 1.0 / B if reduction == "mean" else 1.0
     if reduction == "sum":
