@@ -112,16 +112,19 @@ def ragged_lengths(N, T, U, rng, pair_without_labels=False):
 
 
 # ----------------------------------------------------------------------------- the call forms of a side library
-def call_forms(x, form, one, fwd, bwd, ws_bytes, scale=None, grads=None, stream=None):
-    """One C-ABI call form of a side library -> (status, costs, grads or None).  form: one | two | inplace | score | host.
-    one(grads_ptr or None, costs_ptr, ws_ptr), fwd(costs_ptr, ws_ptr) and bwd(grads_ptr, scale_ptr or None, ws_ptr) call the
-    library's three entries with its own arguments around these.  Costs and gradients start as NaN; `host` hands the entry a
-    host array for the costs, `inplace` the logits for the gradients, `score` no gradients."""
+def call_forms(x, form, one, fwd, bwd, ws_bytes, scale=None, grads=None, stream=None, ws=None):
+    """One C-ABI call form of a side library -> (status, costs, grads or None).  form: one | two | inplace | score | host, and
+    the halves of `two` on their own, fwd | bwd.  one(grads_ptr or None, costs_ptr, ws_ptr), fwd(costs_ptr, ws_ptr) and
+    bwd(grads_ptr, scale_ptr or None, ws_ptr) call the library's three entries with its own arguments around these.  Costs and
+    gradients start as NaN; `host` hands the entry a host array for the costs, `inplace` the logits for the gradients, `score`
+    no gradients.  ws: the caller's workspace (anything with a data_ptr(), of ws_bytes bytes or more) in place of a fresh
+    torch.empty: tests/ws_contract.py plants its contents and its guards."""
     N = x.shape[0]
     cdt = torch.float64 if x.dtype == torch.float64 else torch.float32
     costs = torch.full((N,), float("nan"), dtype=cdt, device=DEV)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=DEV)
-    if grads is None and form not in ("score", "inplace", "host"):
+    if ws is None:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=DEV)
+    if grads is None and form not in ("score", "inplace", "host", "fwd"):
         grads = torch.full_like(x, float("nan"))
     if form in ("one", "score", "inplace", "host"):
         g = None if form == "score" else (x if form == "inplace" else grads)
@@ -133,9 +136,13 @@ def call_forms(x, form, one, fwd, bwd, ws_bytes, scale=None, grads=None, stream=
         st = one(gp, costs.data_ptr(), ws.data_ptr())
         (stream or torch.cuda.current_stream()).synchronize()
         return st, costs.cpu().numpy(), (None if g is None else g.double().cpu().numpy())
-    st = fwd(costs.data_ptr(), ws.data_ptr())
-    assert st == 0
+    if form != "bwd":
+        st = fwd(costs.data_ptr(), ws.data_ptr())
+        assert st == 0
+        if form == "fwd":
+            torch.cuda.synchronize()
+            return st, costs.cpu().numpy(), None
     sc = None if scale is None else torch.tensor(scale, dtype=cdt, device=DEV)
     st = bwd(grads.data_ptr(), sc.data_ptr() if sc is not None else None, ws.data_ptr())
     torch.cuda.synchronize()
-    return st, costs.cpu().numpy(), grads.double().cpu().numpy()
+    return st, (None if form == "bwd" else costs.cpu().numpy()), grads.double().cpu().numpy()

@@ -57,7 +57,7 @@ def _table_problem(name, dtype, N, T, U, A, blank, seed=None):
     return _problem(name, dtype, N, T, U, A, (tl, ll), F.windows(case, tl, ll, rng), rng=rng, blank=blank)
 
 
-def call(x, labels, tl, ll, lo, hi, blank=0, form="one", scale=None, grads=None, stream=None, null=()):
+def call(x, labels, tl, ll, lo, hi, blank=0, form="one", scale=None, grads=None, stream=None, null=(), ws=None):
     """One C-ABI call form -> (status, costs, grads or None).  form: one | two | inplace | score | host."""
     m = _ar()
     N, T, U, A = x.shape
@@ -73,7 +73,7 @@ def call(x, labels, tl, ll, lo, hi, blank=0, form="one", scale=None, grads=None,
         lambda gp, costs, ws: lib.compute_rnnt_loss_ar(x.data_ptr(), gp, *lens, costs, ws, opt, code),
         lambda costs, ws: lib.compute_rnnt_loss_ar_fwd(x.data_ptr(), *lens, costs, ws, opt, code, 1),
         lambda gp, sc, ws: lib.compute_rnnt_loss_ar_bwd(x.data_ptr(), gp, sc, A, N, ws, opt, code),
-        m.workspace_bytes(T, U, N, code), scale, grads, stream)
+        m.workspace_bytes(T, U, N, code), scale, grads, stream, ws)
 
 
 def _reference(x, labels, tl, ll, lo, hi, blank=0, weights=None):

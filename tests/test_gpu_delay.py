@@ -59,7 +59,7 @@ def _frames_buffer(x):
     return torch.full((x.shape[0], x.shape[2] - 1), float("nan"), dtype=cdt, device=DEV)
 
 
-def call(x, labels, tl, ll, blank=0, penalty=PEN, form="one", scale=None, grads=None, stream=None, emit=True, prepare=1):
+def call(x, labels, tl, ll, blank=0, penalty=PEN, form="one", scale=None, grads=None, stream=None, emit=True, prepare=1, ws=None):
     """One C-ABI call form -> (status, costs, grads or None, emit_frames or None).  form: one | two | inplace | score | host.
     emit: True (a NaN buffer of this call's own), a tensor, or False / None (NULL)."""
     m = _delay()
@@ -77,7 +77,7 @@ def call(x, labels, tl, ll, blank=0, penalty=PEN, form="one", scale=None, grads=
         lambda gp, costs, ws: lib.compute_rnnt_loss_delay(x.data_ptr(), penalty, gp, *lens, costs, ep, ws, opt, code),
         lambda costs, ws: lib.compute_rnnt_loss_delay_fwd(x.data_ptr(), penalty, *lens, costs, ep, ws, opt, code, prepare),
         lambda gp, sc, ws: lib.compute_rnnt_loss_delay_bwd(x.data_ptr(), gp, sc, A, N, ws, opt, code),
-        m.workspace_bytes(T, U, N, code), scale, grads, stream)
+        m.workspace_bytes(T, U, N, code), scale, grads, stream, ws)
     torch.cuda.synchronize()
     return st, c, g, (None if fr is None else fr.double().cpu().numpy())
 

@@ -45,7 +45,7 @@ def _problem(name, dtype, N, T, U, A, blank, rng=None, lengths=None, scale=2.0):
     return x, labels, tl, ll, mask
 
 
-def call(x, labels, tl, ll, blank=0, form="one", scale=None, grads=None, stream=None):
+def call(x, labels, tl, ll, blank=0, form="one", scale=None, grads=None, stream=None, ws=None):
     """One C-ABI call form -> (status, costs, grads or None).  form: one | two | inplace | score | host."""
     h = _hat()
     N, T, U, A = x.shape
@@ -59,7 +59,7 @@ def call(x, labels, tl, ll, blank=0, form="one", scale=None, grads=None, stream=
         lambda gp, costs, ws: lib.compute_hat_loss(x.data_ptr(), gp, *lens, costs, ws, opt, code),
         lambda costs, ws: lib.compute_hat_loss_fwd(x.data_ptr(), *lens, costs, ws, opt, code, 1),
         lambda gp, sc, ws: lib.compute_hat_loss_bwd(x.data_ptr(), gp, sc, A, N, ws, opt, code),
-        h.workspace_bytes(T, U, N, code), scale, grads, stream)
+        h.workspace_bytes(T, U, N, code), scale, grads, stream, ws)
 
 
 def _reference(x, labels, tl, ll, blank=0, weights=None, plain=False):

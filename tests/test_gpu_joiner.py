@@ -74,7 +74,7 @@ def _nan_like(shape, dtype, off=0):
 class Problem:
     """One shape of one layout on the device: the index tensors, the C-ABI's argument tail, the reference's arguments."""
 
-    def __init__(self, dtype, layout, act, N, T, U, H, S=0, tl=None, ll=None, ranges=None, off=0):
+    def __init__(self, dtype, layout, act, N, T, U, H, S=0, tl=None, ll=None, ranges=None, off=0, ws=None):
         self.dtype, self.layout, self.act, self.off = dtype, layout, act, off
         self.N, self.T, self.U, self.H, self.S = N, T, U, H, S
         self.tl, self.ll, self.ranges = tl, (None if layout == 2 else ll), ranges
@@ -84,7 +84,8 @@ class Problem:
         self.d_ranges = _dev(ranges, torch.int32) if layout == 2 else None
         self.d_offs = _dev(R.offsets(self.tl, self.ll), torch.int64) if layout == 1 else None
         jn = _jn()
-        self.ws = torch.empty(jn.workspace_bytes(T, U, S, H, N, layout, CODE[dtype]), dtype=torch.uint8, device=DEV)
+        self.ws_bytes = jn.workspace_bytes(T, U, S, H, N, layout, CODE[dtype])
+        self.ws = ws if ws is not None else torch.empty(self.ws_bytes, dtype=torch.uint8, device=DEV)     # (ws: the caller's)
         ptr = lambda t: None if t is None else t.data_ptr()                 # noqa: E731
         self.tail = (layout, R.ACTS.index(act), ptr(self.d_ranges), S, ptr(self.d_offs), ptr(self.d_ll), ptr(self.d_tl), T, U, H, N,
                      self.ws.data_ptr(), options(T, U), CODE[dtype])

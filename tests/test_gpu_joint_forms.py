@@ -73,6 +73,67 @@ def _check_stages(case, names, cus):
 
 
 # ----------------------------------------------------------------------------- the loss entries
+def check_loss(case, oracle, fs, gs, labels, tl, ll, blank, sc, got_c, got_f, got_g):
+    """Costs, df and dg of a loss case against the fp64 oracle on the materialised joint of the stored f and g (CPU tensors),
+    at the module docstring's bounds; sc: the per-sample scale or None.  got_c None: gradients only (a backward call); got_f
+    and got_g None: costs only.  -> the reference df."""
+    N, T, A = fs.shape
+    U = gs.shape[1]
+    dt = fs.dtype
+    lam = case.get("lam", 0.0)
+    # the oracle on the materialised joint of the stored values
+    fr, gr = fs.double().numpy(), gs.double().numpy()
+    z = fr[:, :, None, :] + gr[:, None, :, :]
+    if lam:
+        lp = oracle.log_softmax(z)
+        ref_c, g_lp = oracle.rnnt_logprobs(lp, labels, tl, ll, blank)
+        for b in range(N):
+            for u in range(ll[b]):
+                g_lp[b, :tl[b], u, labels[b, u]] *= 1.0 + lam
+        ref_gz = oracle.chain_rule_to_logits(lp, g_lp)
+    else:
+        ref_c, ref_gz = oracle.rnnt_logits(z, labels, tl, ll, blank)
+    for b in range(N):
+        ref_gz[b, tl[b]:] = 0
+        ref_gz[b, :, ll[b] + 1:] = 0
+    w = np.ones(N) if sc is None else sc.astype(np.float64)
+    rdf = ref_gz.sum(axis=2) * w[:, None, None]
+    rdg = ref_gz.sum(axis=1) * w[:, None, None]
+    what = case["name"]
+    if got_c is None:
+        got_c = ref_c
+    if got_f is None:
+        got_f, got_g = rdf, rdg
+    assert np.isfinite(got_c).all() and np.isfinite(got_f).all() and np.isfinite(got_g).all(), what
+    for b in range(N):                                               # gradient padding: every element written, exactly zero
+        assert not got_f[b, tl[b]:].any() and not got_g[b, ll[b] + 1:].any(), (what, b)
+    big = max(1.0, np.abs(ref_c).max())
+    scale = float(np.abs(w).max())
+    data = case.get("data")
+    if dt == torch.float32:
+        if data is None:                                             # test_against_oracle_on_materialised_joint
+            assert np.abs(got_c - ref_c).max() <= 1e-4 * big, (what, got_c, ref_c)
+            edf = np.abs(got_f - rdf) - (2e-4 * scale * max(1.0, U / 32) + 5e-5 * np.abs(rdf))
+            edg = np.abs(got_g - rdg) - (2e-4 * scale * max(1.0, T / 32) + 5e-5 * np.abs(rdg))
+        else:                                                        # the guard / large-logit tests
+            assert np.abs(got_c - ref_c).max() <= 2e-4 * big, (what, got_c, ref_c)
+            edf = np.abs(got_f - rdf) - (5e-4 * scale + 1e-3 * np.abs(rdf))
+            edg = np.abs(got_g - rdg) - (5e-4 * scale * (max(1.0, T / 32) if data != "far" else 1.0) + 1e-3 * np.abs(rdg))
+    else:
+        assert np.abs(got_c - ref_c).max() <= 1e-4 * big, (what, got_c, ref_c)
+        if data == "far":                                            # test_sixteen_bit_far_cells_and_scale
+            ulp = 2.0 ** -7 if dt == torch.bfloat16 else 2.0 ** -10
+            edf = np.abs(got_f - rdf) - (1e-3 * scale + ulp * (np.abs(rdf) + scale))
+            edg = np.abs(got_g - rdg) - (1e-3 * scale + ulp * (np.abs(rdg) + scale))
+        else:                                                        # test_sixteen_bit_activations / _bf16_case
+            ulp = 2.0 ** -8 if dt == torch.bfloat16 else 2.0 ** -11
+            edf = np.abs(got_f - rdf) - (2e-4 * scale * max(1.0, U / 32) + ulp * np.abs(rdf) + 1e-6)
+            edg = np.abs(got_g - rdg) - (2e-4 * scale * max(1.0, T / 32) + ulp * np.abs(rdg) + 1e-6)
+    assert edf.max() <= 0, (what, "df", edf.max(), np.unravel_index(edf.argmax(), edf.shape))
+    assert edg.max() <= 0, (what, "dg", edg.max(), np.unravel_index(edg.argmax(), edg.shape))
+    return rdf
+
+
 def run_loss_case(case, oracle, cus):
     from warprnnt_pytorch import _lib
     lib = _lib.lib()
@@ -126,55 +187,9 @@ def run_loss_case(case, oracle, cus):
     assert st == 0, (case["name"], st)
     reached = _check_stages(case, names, cus)
 
-    # the oracle on the materialised joint of the stored values
-    fr, gr = fs.double().numpy(), gs.double().numpy()
-    z = fr[:, :, None, :] + gr[:, None, :, :]
-    if lam:
-        lp = oracle.log_softmax(z)
-        ref_c, g_lp = oracle.rnnt_logprobs(lp, labels, tl, ll, blank)
-        for b in range(N):
-            for u in range(ll[b]):
-                g_lp[b, :tl[b], u, labels[b, u]] *= 1.0 + lam
-        ref_gz = oracle.chain_rule_to_logits(lp, g_lp)
-    else:
-        ref_c, ref_gz = oracle.rnnt_logits(z, labels, tl, ll, blank)
-    for b in range(N):
-        ref_gz[b, tl[b]:] = 0
-        ref_gz[b, :, ll[b] + 1:] = 0
-    w = np.ones(N) if sc is None else sc.astype(np.float64)
-    rdf = ref_gz.sum(axis=2) * w[:, None, None]
-    rdg = ref_gz.sum(axis=1) * w[:, None, None]
-    got_c = costs.double().cpu().numpy()
-    got_f, got_g = df.double().cpu().numpy(), dg.double().cpu().numpy()
-    what = case["name"]
-    assert np.isfinite(got_c).all() and np.isfinite(got_f).all() and np.isfinite(got_g).all(), what
-    for b in range(N):                                               # gradient padding: every element written, exactly zero
-        assert not got_f[b, tl[b]:].any() and not got_g[b, ll[b] + 1:].any(), (what, b)
-    big = max(1.0, np.abs(ref_c).max())
-    scale = float(np.abs(w).max())
-    data = case.get("data")
-    if dt == torch.float32:
-        if data is None:                                             # test_against_oracle_on_materialised_joint
-            assert np.abs(got_c - ref_c).max() <= 1e-4 * big, (what, got_c, ref_c)
-            edf = np.abs(got_f - rdf) - (2e-4 * scale * max(1.0, U / 32) + 5e-5 * np.abs(rdf))
-            edg = np.abs(got_g - rdg) - (2e-4 * scale * max(1.0, T / 32) + 5e-5 * np.abs(rdg))
-        else:                                                        # the guard / large-logit tests
-            assert np.abs(got_c - ref_c).max() <= 2e-4 * big, (what, got_c, ref_c)
-            edf = np.abs(got_f - rdf) - (5e-4 * scale + 1e-3 * np.abs(rdf))
-            edg = np.abs(got_g - rdg) - (5e-4 * scale * (max(1.0, T / 32) if data != "far" else 1.0) + 1e-3 * np.abs(rdg))
-    else:
-        assert np.abs(got_c - ref_c).max() <= 1e-4 * big, (what, got_c, ref_c)
-        if data == "far":                                            # test_sixteen_bit_far_cells_and_scale
-            ulp = 2.0 ** -7 if dt == torch.bfloat16 else 2.0 ** -10
-            edf = np.abs(got_f - rdf) - (1e-3 * scale + ulp * (np.abs(rdf) + scale))
-            edg = np.abs(got_g - rdg) - (1e-3 * scale + ulp * (np.abs(rdg) + scale))
-        else:                                                        # test_sixteen_bit_activations / _bf16_case
-            ulp = 2.0 ** -8 if dt == torch.bfloat16 else 2.0 ** -11
-            edf = np.abs(got_f - rdf) - (2e-4 * scale * max(1.0, U / 32) + ulp * np.abs(rdf) + 1e-6)
-            edg = np.abs(got_g - rdg) - (2e-4 * scale * max(1.0, T / 32) + ulp * np.abs(rdg) + 1e-6)
-    assert edf.max() <= 0, (what, "df", edf.max(), np.unravel_index(edf.argmax(), edf.shape))
-    assert edg.max() <= 0, (what, "dg", edg.max(), np.unravel_index(edg.argmax(), edg.shape))
-    _check_data(case, fr, gr, rdf, tl)
+    rdf = check_loss(case, oracle, fs, gs, labels, tl, ll, blank, sc, costs.double().cpu().numpy(), df.double().cpu().numpy(),
+                     dg.double().cpu().numpy())
+    _check_data(case, fs.double().numpy(), gs.double().numpy(), rdf, tl)
     return reached
 
 

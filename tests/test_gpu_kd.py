@@ -48,7 +48,7 @@ def _problem(name, dtype, N, T, U, A, blank, rng=None, lengths=None, scale=2.0):
     return out[0], out[1], labels, tl, ll, mask
 
 
-def call(z, w, labels, tl, ll, blank=0, mode=0, tau=1.0, form="one", scale=None, grads=None, stream=None):
+def call(z, w, labels, tl, ll, blank=0, mode=0, tau=1.0, form="one", scale=None, grads=None, stream=None, ws=None):
     """One C-ABI call form -> (status, costs, grads or None).  form: one | two | inplace | score | host.  z, w on the device."""
     k = _kd()
     N, T, U, A = z.shape
@@ -63,7 +63,7 @@ def call(z, w, labels, tl, ll, blank=0, mode=0, tau=1.0, form="one", scale=None,
         lambda gp, costs, ws: lib.compute_kd_loss(z.data_ptr(), w.data_ptr(), gp, *lens, costs, ws, opt, code, mode, tau),
         lambda costs, ws: lib.compute_kd_loss_fwd(z.data_ptr(), w.data_ptr(), *lens, costs, ws, opt, code, mode, tau, 1),
         lambda gp, sc, ws: lib.compute_kd_loss_bwd(z.data_ptr(), w.data_ptr(), gp, sc, A, N, ws, opt, code, mode, tau),
-        k.workspace_bytes(T, U, N, code), scale, grads, stream)
+        k.workspace_bytes(T, U, N, code), scale, grads, stream, ws)
 
 
 def _f64(x):

@@ -53,7 +53,7 @@ def _arrays(cols, durs):
     return (C.c_int * max(len(cols), 1))(*cols), (C.c_int * max(len(durs), 1))(*durs)
 
 
-def call(x, labels, tl, ll, cols, durs, blank=0, form="one", scale=None, grads=None, sigma=0.0, stream=None, K=None):
+def call(x, labels, tl, ll, cols, durs, blank=0, form="one", scale=None, grads=None, sigma=0.0, stream=None, K=None, ws=None):
     """One C-ABI call form -> (status, costs, grads or None).  form: one | two | inplace | score | host."""
     m = _mb()
     N, T, U, A = x.shape
@@ -69,7 +69,7 @@ def call(x, labels, tl, ll, cols, durs, blank=0, form="one", scale=None, grads=N
         lambda gp, costs, ws: lib.compute_mblank_loss(x.data_ptr(), gp, carr, darr, K, sigma, *lens, costs, ws, opt, code),
         lambda costs, ws: lib.compute_mblank_loss_fwd(x.data_ptr(), carr, darr, K, sigma, *lens, costs, ws, opt, code, 1),
         lambda gp, sc, ws: lib.compute_mblank_loss_bwd(x.data_ptr(), gp, sc, carr, darr, K, A, N, ws, opt, code),
-        m.workspace_bytes(T, U, N, min(max(K, 0), 8), code), scale, grads, stream)
+        m.workspace_bytes(T, U, N, min(max(K, 0), 8), code), scale, grads, stream, ws)
 
 
 def _reference(x, labels, tl, ll, cols, durs, blank=0, sigma=0.0, weights=None):

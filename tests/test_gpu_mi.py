@@ -58,7 +58,8 @@ def _table_problem(case, seed=None):
 
 def call(px, py, bd=None, form="one", scale=None, gx=None, gy=None, ws=None, stream=None, prepare=None):
     """One C-ABI call form on device tensors -> (status, scores, px_grad, py_grad) as numpy (gradients float64, None where the
-    form has none).  form: one | two | score | host.  Scores and gradients start as NaN."""
+    form has none).  form: one | two | score | host, and the halves of `two` on the workspace `ws`, fwd | bwd.  Scores and
+    gradients start as NaN."""
     m = _mi()
     N, S1, T = py.shape
     S, mod = S1 - 1, int(px.shape[2] == T)
@@ -73,12 +74,13 @@ def call(px, py, bd=None, form="one", scale=None, gx=None, gy=None, ws=None, str
         ws = torch.empty(m.workspace_bytes(S, T, N, mod, code), dtype=torch.uint8, device=DEV)
     scores = torch.full((N,), float("nan"), dtype=cdt, device=DEV)
     opt = _opt(stream)
-    if form != "score":
+    nograd = form in ("score", "fwd")
+    if not nograd:
         gx = torch.full_like(px, float("nan")) if gx is None else gx
         gy = torch.full_like(py, float("nan")) if gy is None else gy
-    gxp = None if form == "score" else (gx.data_ptr() if gx.numel() else None)
-    gyp = None if form == "score" else gy.data_ptr()
-    out = lambda t: None if t is None or form == "score" else t.double().cpu().numpy()     # noqa: E731
+    gxp = None if nograd else (gx.data_ptr() if gx.numel() else None)
+    gyp = None if nograd else gy.data_ptr()
+    out = lambda t: None if t is None or nograd else t.double().cpu().numpy()     # noqa: E731
     if form == "host":
         hc = np.full(N, np.nan, dtype=np.float64 if dtype == "f64" else np.float32)
         st = lib.compute_rnnt_mi(xp, py.data_ptr(), bp, S, T, N, mod, hc.ctypes.data, gxp, gyp, ws.data_ptr(), opt, code)
@@ -86,9 +88,12 @@ def call(px, py, bd=None, form="one", scale=None, gx=None, gy=None, ws=None, str
     if form in ("one", "score"):
         st = lib.compute_rnnt_mi(xp, py.data_ptr(), bp, S, T, N, mod, scores.data_ptr(), gxp, gyp, ws.data_ptr(), opt, code)
     else:
-        st = lib.compute_rnnt_mi_fwd(xp, py.data_ptr(), bp, S, T, N, mod, scores.data_ptr(), ws.data_ptr(), opt, code,
-                                     1 if prepare is None else prepare)
-        assert st == 0
+        st = 0
+        if form != "bwd":
+            st = lib.compute_rnnt_mi_fwd(xp, py.data_ptr(), bp, S, T, N, mod, scores.data_ptr(), ws.data_ptr(), opt, code,
+                                         1 if prepare is None else prepare)
+            assert st == 0
+    if form in ("two", "bwd"):
         sc = None if scale is None else torch.tensor(np.asarray(scale, np.float64), dtype=cdt, device=DEV)
         st = lib.compute_rnnt_mi_bwd(gxp, gyp, None if sc is None else sc.data_ptr(), S, T, N, mod, ws.data_ptr(), opt, code)
     torch.cuda.synchronize()

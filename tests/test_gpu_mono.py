@@ -48,7 +48,7 @@ def _problem(name, dtype, N, T, U, A, lengths, rng=None, scale=2.0, blank=None):
     return x, labels, tl, ll, mask
 
 
-def call(x, labels, tl, ll, blank=0, form="one", scale=None, grads=None, stream=None, ws_fill=None):
+def call(x, labels, tl, ll, blank=0, form="one", scale=None, grads=None, stream=None, ws_fill=None, ws=None):
     """One C-ABI call form -> (status, costs, grads or None).  form: one | two | inplace | score | host."""
     m = _mono()
     N, T, U, A = x.shape
@@ -62,7 +62,7 @@ def call(x, labels, tl, ll, blank=0, form="one", scale=None, grads=None, stream=
         lambda gp, costs, ws: lib.compute_rnnt_loss_mono(x.data_ptr(), gp, *lens, costs, ws, opt, code),
         lambda costs, ws: lib.compute_rnnt_loss_mono_fwd(x.data_ptr(), *lens, costs, ws, opt, code, 1),
         lambda gp, sc, ws: lib.compute_rnnt_loss_mono_bwd(x.data_ptr(), gp, sc, A, N, ws, opt, code),
-        m.workspace_bytes(T, U, N, code), scale, grads, stream)
+        m.workspace_bytes(T, U, N, code), scale, grads, stream, ws)
 
 
 def _reference(x, labels, tl, ll, blank=0, weights=None):

@@ -71,7 +71,7 @@ def _problem(name, dtype, N, T, U, A, S, rng=None):
     return x, labels, tl, ll, ranges, mask
 
 
-def call(x, labels, tl, ll, ranges, S, U, form="one", scale=None, grads=None, blank=0, stream=None):
+def call(x, labels, tl, ll, ranges, S, U, form="one", scale=None, grads=None, blank=0, stream=None, ws=None):
     """One C-ABI call form -> (status, costs, grads or None).  form: one | two | inplace | score | host."""
     pl = _pl()
     N, T, A = x.shape[0], x.shape[1], x.shape[3]
@@ -85,7 +85,7 @@ def call(x, labels, tl, ll, ranges, S, U, form="one", scale=None, grads=None, bl
         lambda gp, costs, ws: lib.compute_rnnt_loss_pruned(x.data_ptr(), gp, tr.data_ptr(), S, *lens, costs, ws, opt, code),
         lambda costs, ws: lib.compute_rnnt_loss_pruned_fwd(x.data_ptr(), tr.data_ptr(), S, *lens, costs, ws, opt, code, 1),
         lambda gp, sc, ws: lib.compute_rnnt_loss_pruned_bwd(x.data_ptr(), gp, sc, S, A, N, ws, opt, code),
-        pl.workspace_bytes(T, U, N, code), scale, grads, stream)
+        pl.workspace_bytes(T, U, N, code), scale, grads, stream, ws)
 
 
 def _reference(x, labels, tl, ll, ranges, weights=None):
@@ -127,6 +127,10 @@ def _run_loss_case(case, cus):
     xv = place(x.to(DEV), case.get("off", 0), x.dtype)
     gv = place(torch.full_like(x, float("nan")).to(DEV), case.get("off", 0), x.dtype)
     (st, c, g), names = profiled(lambda: call(xv, labels, tl, ll, ranges, S, U, "one", grads=gv))
+    if st == 0 and not any(P.stage_of(n) for n in names):     # (a profiler session now and then records no device event of
+        print(case["name"], "no kernel of the library recorded:", names)     # the call at all: one more session, judged as the
+        gv.fill_(float("nan"))                                     # first would have been)
+        (st, c, g), names = profiled(lambda: call(xv, labels, tl, ll, ranges, S, U, "one", grads=gv))
     assert st == 0
     _check_stages(case, names, cus)
     assert not any(n.startswith(("rnnt::row_stats", "rnnt::grad_flat_kernel", "rnnt::grad_rows_kernel")) for n in names)
@@ -157,6 +161,10 @@ def _run_ranges_case(case, cus):
         torch.cuda.synchronize()
         return st
     st, names = profiled(run)
+    if st == 0 and not any(P.stage_of(n) for n in names):     # (as _run_loss_case: one more session after an empty one)
+        print(case["name"], "no kernel of the library recorded:", names)
+        out.fill_(-7)
+        st, names = profiled(run)
     assert st == 0
     _check_stages(case, names, cus)
     r = out.cpu().numpy()

@@ -63,7 +63,7 @@ def _shape(dtype, typ, N, T, U, S, A, blank, **kw):
     return dict(dtype=dtype, type=typ, N=N, T=T, U=U, S=S, A=A, blank=blank, **kw)
 
 
-def call(x, labels, s, tl, ll, U, blank=0, typ=0, penalty=PEN, form="one", scale=None, grads=None, stream=None, prepare=1):
+def call(x, labels, s, tl, ll, U, blank=0, typ=0, penalty=PEN, form="one", scale=None, grads=None, stream=None, prepare=1, ws=None):
     """One C-ABI call form -> (status, costs, grads or None).  form: one | two | inplace | score | host."""
     m = _ps()
     N, T, S, A = x.shape
@@ -80,7 +80,7 @@ def call(x, labels, s, tl, ll, U, blank=0, typ=0, penalty=PEN, form="one", scale
         lambda costs, ws: lib.compute_rnnt_loss_pstream_fwd(x.data_ptr(), rg.data_ptr(), S, typ, penalty, *lens, costs, ws, opt,
                                                             code, prepare),
         lambda gp, sc, ws: lib.compute_rnnt_loss_pstream_bwd(x.data_ptr(), gp, sc, S, A, N, ws, opt, code),
-        m.workspace_bytes(T, U, S, N, code), scale, grads, stream)
+        m.workspace_bytes(T, U, S, N, code), scale, grads, stream, ws)
     torch.cuda.synchronize()
     return st, c, g
 

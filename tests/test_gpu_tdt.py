@@ -37,7 +37,7 @@ def _problem(name, dtype, N, T, U, A, durations, rng=None, lengths=None, scale=2
     return x, labels, tl, ll, mask
 
 
-def call(x, labels, tl, ll, durations, form="one", scale=None, grads=None, blank=0, sigma=0.0, stream=None):
+def call(x, labels, tl, ll, durations, form="one", scale=None, grads=None, blank=0, sigma=0.0, stream=None, ws=None):
     """One C-ABI call form -> (status, costs, grads or None).  form: one | two | inplace | score | host."""
     t = _tdt()
     N, T, U, W = x.shape
@@ -54,7 +54,7 @@ def call(x, labels, tl, ll, durations, form="one", scale=None, grads=None, blank
         lambda gp, costs, ws: lib.compute_tdt_loss(x.data_ptr(), gp, dur, D, sigma, *lens, costs, ws, opt, code),
         lambda costs, ws: lib.compute_tdt_loss_fwd(x.data_ptr(), dur, D, sigma, *lens, costs, ws, opt, code, 1),
         lambda gp, sc, ws: lib.compute_tdt_loss_bwd(x.data_ptr(), gp, sc, dur, D, A, N, ws, opt, code),
-        t.workspace_bytes(T, U, N, D, code), scale, grads, stream)
+        t.workspace_bytes(T, U, N, D, code), scale, grads, stream, ws)
 
 
 def _reference(x, labels, tl, ll, durations, blank=0, sigma=0.0, weights=None):

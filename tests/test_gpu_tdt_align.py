@@ -38,12 +38,13 @@ def _mod():
 class Buffers:
     """The device arrays of one call: outputs that start as NaN / UNSET, the workspace, labels and lengths."""
 
-    def __init__(self, x, labels, tl, ll, D):
+    def __init__(self, x, labels, tl, ll, D, ws=None):
         N, T, U, _ = x.shape
         self.score = torch.full((N,), float("nan"), dtype=torch.float64, device=DEV)
         self.frames = torch.full((N, max(U - 1, 1)), UNSET, dtype=torch.int32, device=DEV)
         self.durs = torch.full((N, max(U - 1, 1)), UNSET, dtype=torch.int32, device=DEV)
-        self.ws = torch.empty(_mod().workspace_bytes(T, U, N, D, CODE[NAME[x.dtype]]), dtype=torch.uint8, device=DEV)
+        self.ws = ws if ws is not None else torch.empty(_mod().workspace_bytes(T, U, N, D, CODE[NAME[x.dtype]]),
+                                                        dtype=torch.uint8, device=DEV)
         self.lab, self.tl, self.ll = dev(labels if labels.size else np.zeros((N, 1), np.int32), tl, ll)
 
     def results(self, U):
@@ -60,9 +61,9 @@ def enqueue(x, buf, durations, blank=0, sigma=0.0, stream=None):
                                           CODE[NAME[x.dtype]])
 
 
-def call(x, labels, tl, ll, durations, blank=0, sigma=0.0):
-    """One C-ABI call on the device tensor x -> (status, score, frames, durs)."""
-    buf = Buffers(x, labels, tl, ll, len(durations))
+def call(x, labels, tl, ll, durations, blank=0, sigma=0.0, ws=None):
+    """One C-ABI call on the device tensor x -> (status, score, frames, durs).  ws: the caller's workspace."""
+    buf = Buffers(x, labels, tl, ll, len(durations), ws)
     st = enqueue(x, buf, durations, blank, sigma)
     torch.cuda.synchronize()
     return (st,) + buf.results(x.shape[2])
