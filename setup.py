@@ -12,7 +12,8 @@ include/rnnt_ar.h for warprnnt_pytorch.ar, lib/libwarprnnt_kd.so + include/rnnt_
 lib/libwarprnnt_delay.so + include/rnnt_delay.h for warprnnt_pytorch.delay, lib/libwarprnnt_mi.so + include/rnnt_mi.h for
 warprnnt_pytorch.mi, lib/libwarprnnt_pstream.so + include/rnnt_pstream.h for warprnnt_pytorch.pstream and
 lib/libwarprnnt_joiner.so + include/rnnt_joiner.h for warprnnt_pytorch.joiner, lib/libwarprnnt_logprobs.so +
-include/rnnt_logprobs.h for warprnnt_pytorch.logprobs when those libraries
+include/rnnt_logprobs.h for warprnnt_pytorch.logprobs, lib/libwarprnnt_bestpath.so + include/rnnt_bestpath.h for
+warprnnt_pytorch.bestpath when those libraries
 were built (or lie beside a WARP_RNNT_PATH library);
 no sys.path edits, no environment variables at run time (a WARP_RNNT_PATH naming ANOTHER library at run time is honoured by switching to
 the ctypes loader: the compiled module is linked to the library it was built with).
@@ -31,7 +32,7 @@ from setuptools.dist import Distribution
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 PKG_SRC = os.path.join(ROOT, "warp-transducer_amd", "warprnnt_pytorch")
-SIDE = ("pruned", "tdt", "hat", "mblank", "tdt_align", "mono", "ar", "kd", "delay") + ("mi",) + ("pstream",) + ("joiner",) + ("logprobs",)      # warprnnt_pytorch.NAME loads lib/libwarprnnt_NAME.so (include/rnnt_NAME.h)
+SIDE = ("pruned", "tdt", "hat", "mblank", "tdt_align", "mono", "ar", "kd", "delay") + ("mi",) + ("pstream",) + ("joiner",) + ("logprobs",) + ("bestpath",)      # warprnnt_pytorch.NAME loads lib/libwarprnnt_NAME.so (include/rnnt_NAME.h)
 SIDE_LIBS = ["libwarprnnt_%s.so" % name for name in SIDE]
 MAKE_LIBS = (["make", "-j3", "-C", os.path.join(ROOT, "warp-transducer_amd"), "lib/libwarprnnt.so"]
              + ["lib/" + so for so in SIDE_LIBS])
