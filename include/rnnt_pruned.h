@@ -17,6 +17,10 @@
  * one-call entry returns RNNT_STATUS_INVALID_VALUE, as for lengths that do not fit the tensor) and zero gradients.  A sample
  * whose windows hold no path costs +inf, with NaN gradients on its in-lattice rows.  With S = maxU and every start 0 this is
  * compute_rnnt_loss_async on the same tensor.  gradients == activations (in place) is allowed; other overlaps are not.
+ *
+ * BATCH SIZE.  The loss takes any minibatch with N maxT S < 2^32 rows (its kernels run the batch in slices of 65535
+ * samples).  compute_rnnt_prune_ranges_add runs the additive joint's partition kernels, which keep the samples on one grid
+ * dimension: minibatch > 65535 -> RNNT_STATUS_INVALID_VALUE, nothing written (as compute_rnnt_loss_add, include/rnnt.h).
  */
 #pragma once
 
@@ -53,7 +57,8 @@ rnntStatus_t compute_rnnt_loss_pruned_bwd(const void* activations, void* gradien
  * with the largest window sum of gamma over [s, min(s + S - 1, L_b)]; clamped into [max(0, smax - (T_b - 1 - t)(S - 1)),
  * min(smax, t (S - 1))]; made non-decreasing (forward pass); consecutive windows made to overlap (backward pass,
  * s_t = max(s_t, s_{t+1} - (S - 1))); frames t >= T_b get 0.  When L_b <= T_b (S - 1) a path through the windows exists
- * (s_0 = 0, steps in [0, S - 1], s_{T_b - 1} = smax); otherwise s_t = min(t (S - 1), smax).  Writes ranges (N, maxT). */
+ * (s_0 = 0, steps in [0, S - 1], s_{T_b - 1} = smax); otherwise s_t = min(t (S - 1), smax).  Writes ranges (N, maxT).
+ * minibatch <= 65535 (BATCH SIZE above). */
 rnntStatus_t compute_rnnt_prune_ranges_add(const void* trans_acts, const void* pred_acts, const int* flat_labels,
                                            const int* label_lengths, const int* input_lengths, int alphabet_size,
                                            int minibatch, int S, int* ranges, void* workspace, rnntOptions options,

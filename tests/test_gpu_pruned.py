@@ -60,9 +60,9 @@ def _assert_real_lattice(c, tl, ll, ranges, S, what):
         assert any(np.isfinite(c[b]) and ll[b] > 0 for b in range(len(c))), (what, c, ll)
 
 
-def _problem(name, dtype, N, T, U, A, S, rng=None):
+def _problem(name, dtype, N, T, U, A, S, rng=None, lengths=None):
     rng = rng or np.random.default_rng(zlib.crc32(name.encode()))
-    tl, ll = ragged_lengths(N, T, U, rng)
+    tl, ll = lengths if lengths is not None else ragged_lengths(N, T, U, rng)
     labels = rng.integers(1, A, size=(N, U - 1)).astype(np.int32) if A > 1 else np.zeros((N, U - 1), np.int32)
     ranges = _windows(N, T, S, tl, ll, rng)
     x = torch.tensor(rng.standard_normal((N, T, S, A)) * 2.0, dtype=torch.float32).to(TORCH[dtype])

@@ -165,14 +165,15 @@ def _nan_grads(x, off):
 
 
 def _logits_library(module, build, nbytes, names=("costs", "grads")):
-    """problem(case, variant) of a loss on one logits tensor: build(M, case) -> (x, rest, kw) with M.call(x, *rest, **kw, form=,
-    scale=, grads=, ws=); the failing batch is the healthy one with a NaN row in every sample."""
+    """problem(case, variant) of a loss on one logits tensor: build(M, case) -> (x, rest, kw, mask) with M.call(x, *rest, **kw,
+    form=, scale=, grads=, ws=) and mask the rows the module's checker compares (tests/side_limits.py repeats such a batch);
+    the failing batch is the healthy one with a NaN row in every sample."""
     def problem(case, variant, cus):
         M = importlib.import_module("tests.test_gpu_" + module)
         case = _resolve(case, cus)
         if variant == "grown":
             case = _grown(case, lengths=None) if "lengths" in case else _grown(case)
-        x, rest, kw = build(M, case)
+        x, rest, kw, _ = build(M, case)
         off = case.get("off", 0)
         hit = None
         if variant == "failing":
@@ -202,48 +203,63 @@ def _code(x):
 
 
 # ----------------------------------------------------------------------------- the side libraries
+def _lengths(c):
+    """A case's own (T_b, L_b), where it has them (tests/side_limits.py: full-length samples); else the module's ragged ones."""
+    ln = c.get("lengths")
+    return None if ln is None else (np.asarray(ln[0], np.int32), np.asarray(ln[1], np.int32))
+
+
+def _pruned(M, c):
+    x, labels, tl, ll, ranges, mask = M._problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["S"],
+                                                 lengths=_lengths(c))
+    return x, (labels, tl, ll, ranges, c["S"], c["U"]), {}, mask
+
+
 def _hat(M, c):
-    x, labels, tl, ll, _ = M._problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["blank"])
-    return x, (labels, tl, ll), dict(blank=c["blank"])
+    x, labels, tl, ll, mask = M._problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["blank"],
+                                         lengths=_lengths(c))
+    return x, (labels, tl, ll), dict(blank=c["blank"]), mask
 
 
 def _tdt(M, c):
-    x, labels, tl, ll, _ = M._problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["durations"])
-    return x, (labels, tl, ll, c["durations"]), {}
+    x, labels, tl, ll, mask = M._problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["durations"],
+                                         lengths=_lengths(c))
+    return x, (labels, tl, ll, c["durations"]), {}, mask
 
 
 def _mblank(M, c):
-    x, labels, tl, ll, _ = M._problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["blank"], c["columns"],
-                                      lengths=c.get("lengths"))
-    return x, (labels, tl, ll, c["columns"], c["durations"]), dict(blank=c["blank"])
+    x, labels, tl, ll, mask = M._problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["blank"], c["columns"],
+                                         lengths=_lengths(c))
+    return x, (labels, tl, ll, c["columns"], c["durations"]), dict(blank=c["blank"]), mask
 
 
 def _kd(M, c):
-    z, w, labels, tl, ll, _ = M._problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["blank"])
-    return z, (w, labels, tl, ll), dict(blank=c["blank"], mode=c["mode"], tau=1.0)
+    z, w, labels, tl, ll, mask = M._problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["blank"],
+                                            lengths=_lengths(c))
+    return z, (w, labels, tl, ll), dict(blank=c["blank"], mode=c["mode"], tau=1.0), mask
 
 
 def _ar(M, c):
-    x, labels, tl, ll, lo, hi, _ = M._table_problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["blank"])
-    return x, (labels, tl, ll, lo, hi), dict(blank=c["blank"])
+    x, labels, tl, ll, lo, hi, mask = M._table_problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["blank"])
+    return x, (labels, tl, ll, lo, hi), dict(blank=c["blank"]), mask
 
 
 def _delay(M, c):
-    x, labels, tl, ll, _ = M._table_problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["blank"])
-    return x, (labels, tl, ll), dict(blank=c["blank"])
+    x, labels, tl, ll, mask = M._table_problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], c["blank"])
+    return x, (labels, tl, ll), dict(blank=c["blank"]), mask
 
 
 def _pstream(M, c):
-    x, labels, s, tl, ll, _ = M._table_problem(c["name"], c)
-    return x, (labels, s, tl, ll, c["U"]), dict(blank=c["blank"], typ=c["type"])
+    x, labels, s, tl, ll, mask = M._table_problem(c["name"], c)
+    return x, (labels, s, tl, ll, c["U"]), dict(blank=c["blank"], typ=c["type"]), mask
 
 
 def _mono(M, c):
     from tests import mono_forms as F
     rng = _rng(c["name"])
-    x, labels, tl, ll, _ = M._problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], F.lengths(c, rng), rng=rng,
-                                      blank=c["blank"])
-    return x, (labels, tl, ll), dict(blank=c["blank"])
+    x, labels, tl, ll, mask = M._problem(c["name"], c["dtype"], c["N"], c["T"], c["U"], c["A"], F.lengths(c, rng), rng=rng,
+                                         blank=c["blank"])
+    return x, (labels, tl, ll), dict(blank=c["blank"]), mask
 
 
 def _pruned_problem(case, variant, cus):
@@ -276,7 +292,7 @@ def _pruned_problem(case, variant, cus):
         return Called(nbytes, N, call, ("ranges",), forms=("one",), halves=False)
     if case["entry"] == "ranges":
         A, case = min(A, 8), dict(case, off=0)
-    x, labels, tl, ll, ranges, _ = M._problem(case["name"], dtype, N, T, U, A, S)
+    x, (labels, tl, ll, ranges, _, _), _, _ = _pruned(M, dict(case, N=N, T=T, U=U, A=A))
     if variant == "failing":
         x = torch.nan_to_num(x)
         ranges = ranges.copy()

@@ -219,7 +219,8 @@ static bool make_plan(Plan<C>& p, int A, int N, const rnntOptions& opt, void* wo
     if (p.blank < 0 || p.blank >= A) return false;
     if (p.maxU > 1024) return false;               // one lane per label position (as the reference)
     if (static_cast<long long>(p.maxT) * p.maxU > 0x7fffffffLL / 4) return false;
-    if (joint && N > kGridSamples) return false;   // (the additive-joint kernels keep the samples on ONE grid dimension)
+    // (joint: the additive joint's workspace layout.  The batch limit of the additive-joint kernels, which keep the samples
+    //  on ONE grid dimension, is checked where they are launched: run_gpu_joint and run_prune_ranges)
     if (static_cast<long long>(N) * 2 > 0x7fffffffLL) return false;   // lattice kernel: 2 N blocks on gridDim.x
     p.Up = lat_stride(p.maxU);
     // one sample's skewed lp2 array is addressed through a buffer descriptor with a 32-bit size

@@ -131,6 +131,7 @@ rnntStatus_t run_gpu_joint(const typename Tag::store* f, const typename Tag::sto
     constexpr bool k16 = sizeof(typename Tag::store) == 2;
     const int jbits = tune().j16;                          // which stages take the matrix-core form (bit 0 DG, 1 DF, 2 Z)
     Plan<float> p;
+    if (N > kGridSamples) return RNNT_STATUS_INVALID_VALUE;    // the additive-joint kernels keep the samples on ONE grid dimension
     if (!make_plan(p, A, N, opt, workspace, labels, label_lengths, input_lengths, costs_device, /*joint=*/true))
         return RNNT_STATUS_INVALID_VALUE;
     if (!(fastemit >= 0.0f)) return RNNT_STATUS_INVALID_VALUE;

@@ -112,6 +112,7 @@ rnntStatus_t run_prune_ranges(const SideCall& c, const void* pred_acts, int S, i
     const int *label_lengths = c.label_lengths, *input_lengths = c.input_lengths;
     const int A = c.A, N = c.N;
     Plan<float> p;
+    if (N > kGridSamples) return RNNT_STATUS_INVALID_VALUE;    // the partition kernels keep the samples on ONE grid dimension
     if (!make_plan(p, A, N, c.opt, c.workspace, c.labels, label_lengths, input_lengths, static_cast<float*>(nullptr),
                    /*joint=*/true))
         return RNNT_STATUS_INVALID_VALUE;
