@@ -32,7 +32,7 @@ from setuptools.dist import Distribution
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 PKG_SRC = os.path.join(ROOT, "warp-transducer_amd", "warprnnt_pytorch")
-SIDE = ("pruned", "tdt", "hat", "mblank", "tdt_align", "mono", "ar", "kd", "delay") + ("mi",) + ("pstream",) + ("joiner",) + ("logprobs",) + ("bestpath",) + ("expect",) + ("sample",)      # warprnnt_pytorch.NAME loads lib/libwarprnnt_NAME.so (include/rnnt_NAME.h)
+SIDE = ("pruned", "tdt", "hat", "mblank", "tdt_align", "mono", "ar", "kd", "delay") + ("mi",) + ("pstream",) + ("joiner",) + ("logprobs",) + ("bestpath",) + ("expect",) + ("sample",) + ("ranges",)      # warprnnt_pytorch.NAME loads lib/libwarprnnt_NAME.so (include/rnnt_NAME.h)
 SIDE_LIBS = ["libwarprnnt_%s.so" % name for name in SIDE]
 MAKE_LIBS = (["make", "-j3", "-C", os.path.join(ROOT, "warp-transducer_amd"), "lib/libwarprnnt.so"]
              + ["lib/" + so for so in SIDE_LIBS])
