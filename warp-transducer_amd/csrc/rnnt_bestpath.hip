@@ -11,29 +11,6 @@ using namespace rnnt;
 
 namespace {
 
-// A buffer of a call: [p, p + bytes), `elem` the size its address must be a multiple of; p == nullptr: not given.
-struct BpBuf { const void* p; unsigned long long bytes, elem; };
-
-bool bp_overlap(const BpBuf& a, const BpBuf& b) {
-    if (a.p == nullptr || b.p == nullptr || a.bytes == 0 || b.bytes == 0) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
-    return x < y + b.bytes && y < x + a.bytes;
-}
-
-// Every buffer on an element boundary; no output sharing a byte with an input or another output.  true: refused.
-bool bp_bad_buffers(const BpBuf* in, int nin, const BpBuf* out, int nout) {
-    for (int i = 0; i < nin; ++i)
-        if (in[i].p != nullptr && reinterpret_cast<uintptr_t>(in[i].p) % in[i].elem != 0) return true;
-    for (int i = 0; i < nout; ++i) {
-        if (out[i].p != nullptr && reinterpret_cast<uintptr_t>(out[i].p) % out[i].elem != 0) return true;
-        for (int j = 0; j < nin; ++j)
-            if (bp_overlap(out[i], in[j])) return true;
-        for (int j = i + 1; j < nout; ++j)
-            if (bp_overlap(out[i], out[j])) return true;
-    }
-    return false;
-}
-
 bool bp_bad_common(int S, int T, int N, const rnntOptions& o, int dtype_code) {
     return !bp_shape_ok(S, T, N) || dtype_code < 0 || dtype_code > 3 || loc_of(o) != RNNT_GPU;
 }
@@ -54,11 +31,11 @@ rnntStatus_t compute_rnnt_bestpath(const void* px, const void* py, const void* b
     const unsigned long long esz = dtype_code == 1 ? 8 : dtype_code == 0 ? 4 : 2, B = static_cast<unsigned long long>(minibatch);
     const unsigned long long xb = B * S * (modified != 0 ? T : T + 1) * esz, yb = B * (S + 1) * T * esz;
     const bool edges = py_path != nullptr;
-    const BpBuf in[] = {{px, xb, esz}, {py, yb, esz}, {boundary, B * 4 * sizeof(long long), sizeof(long long)}};
-    const BpBuf out[] = {{scores, B * sizeof(double), sizeof(double)}, {frames, B * S * sizeof(int), sizeof(int)},
-                         {back, B * bp_back_words(S, T) * 8, 8}, {edges ? px_path : nullptr, xb, esz},
-                         {edges ? py_path : nullptr, yb, esz}};
-    if (bp_bad_buffers(in, 3, out, 5)) return RNNT_STATUS_INVALID_VALUE;
+    const SideBuf in[] = {{px, xb, esz}, {py, yb, esz}, {boundary, B * 4 * sizeof(long long), sizeof(long long)}};
+    const SideBuf out[] = {{scores, B * sizeof(double), sizeof(double)}, {frames, B * S * sizeof(int), sizeof(int)},
+                           {back, B * bp_back_words(S, T) * 8, 8}, {edges ? px_path : nullptr, xb, esz},
+                           {edges ? py_path : nullptr, yb, esz}};
+    if (side_bad_buffers(in, 3, out, 5)) return RNNT_STATUS_INVALID_VALUE;
     const bool dev = is_device_pointer(scores);
     const BestpathCall c = {px, py, boundary, dev ? scores : nullptr, dev ? nullptr : scores, frames, back, nullptr,
                             px_path, py_path, S, T, minibatch, modified != 0, reinterpret_cast<hipStream_t>(options.stream),
@@ -74,11 +51,11 @@ rnntStatus_t compute_rnnt_bestpath_edges(const int* frames, const void* scores_d
         return RNNT_STATUS_INVALID_VALUE;
     const unsigned long long esz = dtype_code == 1 ? 8 : dtype_code == 0 ? 4 : 2, B = static_cast<unsigned long long>(minibatch);
     const unsigned long long xb = B * S * (modified != 0 ? T : T + 1) * esz, yb = B * (S + 1) * T * esz;
-    const BpBuf in[] = {{frames, B * S * sizeof(int), sizeof(int)}, {scores_device, B * sizeof(double), sizeof(double)},
-                        {boundary, B * 4 * sizeof(long long), sizeof(long long)},
-                        {grad_scale_device, B * sizeof(double), sizeof(double)}};
-    const BpBuf out[] = {{px_path, xb, esz}, {py_path, yb, esz}};
-    if (bp_bad_buffers(in, 4, out, 2)) return RNNT_STATUS_INVALID_VALUE;
+    const SideBuf in[] = {{frames, B * S * sizeof(int), sizeof(int)}, {scores_device, B * sizeof(double), sizeof(double)},
+                          {boundary, B * 4 * sizeof(long long), sizeof(long long)},
+                          {grad_scale_device, B * sizeof(double), sizeof(double)}};
+    const SideBuf out[] = {{px_path, xb, esz}, {py_path, yb, esz}};
+    if (side_bad_buffers(in, 4, out, 2)) return RNNT_STATUS_INVALID_VALUE;
     const BestpathCall c = {nullptr, nullptr, boundary, const_cast<void*>(scores_device), nullptr, const_cast<int*>(frames),
                             nullptr, grad_scale_device, px_path, py_path, S, T, minibatch, modified != 0,
                             reinterpret_cast<hipStream_t>(options.stream), 2};

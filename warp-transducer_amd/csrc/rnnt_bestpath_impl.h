@@ -35,11 +35,7 @@ struct BestpathCall {
     int phases;
 };
 
-static inline bool bp_shape_ok(int S, int T, int N) {
-    if (S < 0 || T < 1 || N < 1 || S + 1 > kBpMaxU) return false;
-    const unsigned long long nodes = static_cast<unsigned long long>(T + 1LL) * (S + 1LL);
-    return nodes < (1ull << 25) && nodes * N < (1ull << 32);
-}
+static inline bool bp_shape_ok(int S, int T, int N) { return side_lattice_ok(S, T, N, kBpMaxU); }
 static inline unsigned long long bp_back_words(int S, int T) {
     return static_cast<unsigned long long>(S + 1) * ((T + 64) >> 6);
 }

@@ -1,14 +1,11 @@
 // rnnt_bestpath_kernels.h -- the gfx950 kernels of the best path over edge log-probabilities (include/rnnt_bestpath.h).
 //
-//   1 bestpath_sweep_kernel   one block per sample.  SWEEP: the max-plus recursion, a thread per K consecutive lattice rows
-//                             (row = s - s0).  Regular type: row r meets t = t0 + d - r on anti-diagonal d; modified type:
-//                             every row meets t = t0 + d.  Either way a thread walks ITS OWN rows px[b, s, :], py[b, s, :] in
-//                             t order -- no transpose, no pack stage, no workspace -- one chunk of kBpChunk steps ahead of
-//                             use.  p, the emit candidate p + px and the stay candidate p + py are fp64 registers; the left
-//                             neighbour's emit candidate arrives through two DPP moves (wave_shr1) inside a wavefront and
-//                             through one LDS word per wavefront and step parity behind an LDS-only barrier between
-//                             wavefronts.  A thread collects the decision bits of a row 64 frames at a time in a register
-//                             and stores whole words of `back`: no ballot, no atomics, one layout for both types.
+//   1 bestpath_sweep_kernel   one block per sample.  SWEEP: the max-plus recursion on the row-sweep schedule rnnt_pxpy.h
+//                             describes, with a thread per K consecutive lattice rows (row = s - s0) and chunks of
+//                             kBpChunk (K = 1) or kBpChunkWide steps.  p, the emit candidate p + px and the stay candidate
+//                             p + py are fp64 registers; the emit candidate of the thread's LAST row is the value handed
+//                             to the next thread.  A thread collects the decision bits of a row 64 frames at a time in a
+//                             register and stores whole words of `back`: no ballot, no atomics, one layout for both types.
 //                             TRACEBACK, same launch: the block zeroes the words of `back` outside the rectangle and
 //                             frames outside [s0, s1), stages the rectangle's words into LDS a range of rows at a time, and
 //                             thread 0 walks from (s1, t1) to row s0.  The score leaves the block LAST (the host-scores
@@ -16,11 +13,14 @@
 //   2 bestpath_edges_kernel   element-wise over the coordinates (b, s, t) of px_path / py_path, t fastest: reads frames,
 //                             the score and the boundary (block-uniform) and stores both indicators coalesced along t.
 //
-// Loads are element-wise: in the regular type the rows of a wavefront are at 64 different frames, so a lane's position in a
-// 16-byte packet is lane-variant and a packet saves no instruction (DESIGN.md 8o lists the modified type's packets as open).
+// The sweep is HAND-WRITTEN here, not a call of pxpy_sweep.  A port of pxpy_sweep with a rows-per-thread parameter was
+// cross-compiled for gfx950 and matched every form but one: bestpath_sweep_kernel<F64, false, 4, true> uses exactly the 128
+// VGPRs a 1024-thread block allows, and the port spilled 4 of them (20 bytes of scratch) in two variants.  A change to the
+// parity exchange or to a bounds predicate in rnnt_pxpy.h has to be made here as well.
+// (DESIGN.md 8o lists the modified type's 16-byte packets as open.)
 #pragma once
 
-#include "rnnt_kernels.h"              // lds_barrier, cost_invalid; through rnnt_device.h the tags, load1 / store1, wave_shr1
+#include "rnnt_pxpy.h"                 // PxRect / px_rect; through rnnt_kernels.h lds_barrier, cost_invalid, load1 / store1, wave_shr1
 
 namespace rnnt {
 
@@ -29,19 +29,6 @@ constexpr int kBpChunkWide = 2;         // ... with kBpWideRows rows per thread 
 constexpr int kBpWideRows = 4;          // rows per thread above 1024 lattice rows
 constexpr int kBpWaveMaxU = 64;         // S + 1 up to here: one wavefront, no LDS exchange
 constexpr int kBpLdsWords = 6144;       // traceback staging: 48 KB of decision words per range of rows
-
-// The rectangle of sample b: ok == false for a boundary outside the tensor (then s0 = t0 = 0, Sr = -1, Tr = 0).
-struct BpRect { int s0, t0, Sr, Tr; bool ok; };
-__device__ __forceinline__ BpRect bp_rect(const long long* __restrict__ boundary, int b, int S, int T) {
-    long long q0 = 0, r0 = 0, q1 = S, r1 = T;
-    if (boundary != nullptr) {
-        const long long* bd = boundary + static_cast<size_t>(b) * 4;
-        q0 = bd[0]; r0 = bd[1]; q1 = bd[2]; r1 = bd[3];
-    }
-    const bool ok = 0 <= q0 && q0 <= q1 && q1 <= S && 0 <= r0 && r0 <= r1 && r1 <= T;
-    return {ok ? static_cast<int>(q0) : 0, ok ? static_cast<int>(r0) : 0, ok ? static_cast<int>(q1 - q0) : -1,
-            ok ? static_cast<int>(r1 - r0) : 0, ok};
-}
 
 // Thread 0's walk from node (s, t) -- the rectangle's coordinates -- down to row `lo` (row 0 needs no decision): at t == 0 the
 // symbol edge, otherwise the bit.  word(row, w) = word w (absolute) of the row's decision bits.  A word is fetched once per
@@ -86,7 +73,7 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void bestpath_sweep_kernel(
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
     const int nthreads = static_cast<int>(blockDim.x);
     const int TX = MOD ? T : T + 1, U = S + 1, NW = (T + 64) >> 6;
-    const BpRect r = bp_rect(boundary, b, S, T);
+    const PxRect r = px_rect(boundary, b, S, T);
     const int s0 = r.s0, t0 = r.t0, Sr = r.Sr, Tr = r.Tr;
     const double NEG = -__builtin_huge_val(), INF = __builtin_huge_val();
     unsigned long long* bk = back + static_cast<size_t>(b) * U * NW;
@@ -129,7 +116,7 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void bestpath_sweep_kernel(
         };
         C ax[K][CH], ay[K][CH], bx[K][CH], by[K][CH];
         load(0, ax, ay);
-        // The two buffers keep FIXED roles per call site (the loop is unrolled by two chunks), as align_lattice_kernel's.
+        // The two buffers keep FIXED roles per call site (the loop is unrolled by two chunks), as pxpy_sweep's.
         auto chunk = [&](int d0, C (&cx)[K][CH], C (&cy)[K][CH], C (&nx)[K][CH], C (&ny)[K][CH]) {
             if (d0 + CH < nsteps) load(d0 + CH, nx, ny);
 #pragma unroll
@@ -229,7 +216,7 @@ __global__ __launch_bounds__(256) void bestpath_edges_kernel(
     const int b = b0 + blockIdx.z, s = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
     const int TX = MOD ? T : T + 1, U = S + 1;
     if (t > T) return;
-    const BpRect r = bp_rect(boundary, b, S, T);
+    const PxRect r = px_rect(boundary, b, S, T);
     const int s0 = r.s0, t0 = r.t0, s1 = r.s0 + r.Sr, t1 = r.t0 + r.Tr;
     const double sc = scores[static_cast<size_t>(b) * score_stride];
     const bool nan = r.ok && sc != sc, path = r.ok && sc - sc == 0.0;

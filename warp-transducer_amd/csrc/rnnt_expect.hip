@@ -11,30 +11,6 @@ using namespace rnnt;
 
 namespace {
 
-// A buffer of a call: [p, p + bytes), `elem` the size its address must be a multiple of; p == nullptr: not given.
-struct ExBuf { const void* p; unsigned long long bytes, elem; };
-
-bool ex_overlap(const ExBuf& a, const ExBuf& b) {
-    if (a.p == nullptr || b.p == nullptr || a.bytes == 0 || b.bytes == 0) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
-    return x < y + b.bytes && y < x + a.bytes;
-}
-
-// Every buffer on an element boundary; no output sharing a byte with an input or another output (inputs may alias
-// inputs).  true: refused.
-bool ex_bad_buffers(const ExBuf* in, int nin, const ExBuf* out, int nout) {
-    for (int i = 0; i < nin; ++i)
-        if (in[i].p != nullptr && reinterpret_cast<uintptr_t>(in[i].p) % in[i].elem != 0) return true;
-    for (int i = 0; i < nout; ++i) {
-        if (out[i].p != nullptr && reinterpret_cast<uintptr_t>(out[i].p) % out[i].elem != 0) return true;
-        for (int j = 0; j < nin; ++j)
-            if (ex_overlap(out[i], in[j])) return true;
-        for (int j = i + 1; j < nout; ++j)
-            if (ex_overlap(out[i], out[j])) return true;
-    }
-    return false;
-}
-
 bool ex_bad_common(int S, int T, int N, const rnntOptions& o, int dtype_code) {
     return !ex_shape_ok(S, T, N) || dtype_code < 0 || dtype_code > 3 || loc_of(o) != RNNT_GPU;
 }
@@ -66,12 +42,12 @@ rnntStatus_t compute_rnnt_expect(const void* px, const void* py, const void* cx,
         return RNNT_STATUS_INVALID_VALUE;
     const ExSizes z = ex_sizes(S, T, minibatch, modified, dtype_code);
     const bool grads = py_grad != nullptr, cgrads = cy_grad != nullptr;
-    const ExBuf in[] = {{px, z.xb, z.esz}, {py, z.yb, z.esz}, {cx, z.xb, z.esz}, {cy, z.yb, z.esz},
-                        {boundary, z.bd, sizeof(long long)}};
-    const ExBuf out[] = {{scores, z.sc, sizeof(double)}, {expect, z.sc, sizeof(double)}, {nodes, z.nd, 2 * sizeof(double)},
-                         {grads ? px_grad : nullptr, z.xb, z.esz}, {grads ? py_grad : nullptr, z.yb, z.esz},
-                         {cgrads ? cx_grad : nullptr, z.xb, z.esz}, {cgrads ? cy_grad : nullptr, z.yb, z.esz}};
-    if (ex_bad_buffers(in, 5, out, 7)) return RNNT_STATUS_INVALID_VALUE;
+    const SideBuf in[] = {{px, z.xb, z.esz}, {py, z.yb, z.esz}, {cx, z.xb, z.esz}, {cy, z.yb, z.esz},
+                          {boundary, z.bd, sizeof(long long)}};
+    const SideBuf out[] = {{scores, z.sc, sizeof(double)}, {expect, z.sc, sizeof(double)}, {nodes, z.nd, 2 * sizeof(double)},
+                           {grads ? px_grad : nullptr, z.xb, z.esz}, {grads ? py_grad : nullptr, z.yb, z.esz},
+                           {cgrads ? cx_grad : nullptr, z.xb, z.esz}, {cgrads ? cy_grad : nullptr, z.yb, z.esz}};
+    if (side_bad_buffers(in, 5, out, 7)) return RNNT_STATUS_INVALID_VALUE;
     const bool dev = is_device_pointer(scores);
     if (dev != is_device_pointer(expect)) return RNNT_STATUS_INVALID_VALUE;    // both scalars in one kind of memory
     const ExpectCall c = {px, py, cx, cy, boundary, dev ? scores : nullptr, dev ? expect : nullptr, dev ? nullptr : scores,
@@ -88,11 +64,11 @@ rnntStatus_t compute_rnnt_expect_fwd(const void* px, const void* py, const void*
         expect_device == nullptr || nodes == nullptr || (S > 0 && (px == nullptr || cx == nullptr)))
         return RNNT_STATUS_INVALID_VALUE;
     const ExSizes z = ex_sizes(S, T, minibatch, modified, dtype_code);
-    const ExBuf in[] = {{px, z.xb, z.esz}, {py, z.yb, z.esz}, {cx, z.xb, z.esz}, {cy, z.yb, z.esz},
-                        {boundary, z.bd, sizeof(long long)}};
-    const ExBuf out[] = {{scores_device, z.sc, sizeof(double)}, {expect_device, z.sc, sizeof(double)},
-                         {nodes, z.nd, 2 * sizeof(double)}};
-    if (ex_bad_buffers(in, 5, out, 3)) return RNNT_STATUS_INVALID_VALUE;
+    const SideBuf in[] = {{px, z.xb, z.esz}, {py, z.yb, z.esz}, {cx, z.xb, z.esz}, {cy, z.yb, z.esz},
+                          {boundary, z.bd, sizeof(long long)}};
+    const SideBuf out[] = {{scores_device, z.sc, sizeof(double)}, {expect_device, z.sc, sizeof(double)},
+                           {nodes, z.nd, 2 * sizeof(double)}};
+    if (side_bad_buffers(in, 5, out, 3)) return RNNT_STATUS_INVALID_VALUE;
     const ExpectCall c = {px, py, cx, cy, boundary, scores_device, expect_device, nullptr, nullptr, nodes, nullptr, nullptr,
                           nullptr, nullptr, nullptr, nullptr, S, T, minibatch, modified != 0,
                           reinterpret_cast<hipStream_t>(options.stream), 1};
@@ -111,13 +87,13 @@ rnntStatus_t compute_rnnt_expect_bwd(const void* px, const void* py, const void*
     if (ex_one_of_pair(S, cx_grad, cy_grad)) return RNNT_STATUS_INVALID_VALUE;
     const ExSizes z = ex_sizes(S, T, minibatch, modified, dtype_code);
     const bool cgrads = cy_grad != nullptr;
-    const ExBuf in[] = {{px, z.xb, z.esz}, {py, z.yb, z.esz}, {cx, z.xb, z.esz}, {cy, z.yb, z.esz},
-                        {boundary, z.bd, sizeof(long long)}, {nodes, z.nd, 2 * sizeof(double)},
-                        {scores_device, z.sc, sizeof(double)}, {expect_device, z.sc, sizeof(double)},
-                        {g_expect_device, z.sc, sizeof(double)}, {g_score_device, z.sc, sizeof(double)}};
-    const ExBuf out[] = {{px_grad, z.xb, z.esz}, {py_grad, z.yb, z.esz}, {cgrads ? cx_grad : nullptr, z.xb, z.esz},
-                         {cgrads ? cy_grad : nullptr, z.yb, z.esz}};
-    if (ex_bad_buffers(in, 10, out, 4)) return RNNT_STATUS_INVALID_VALUE;
+    const SideBuf in[] = {{px, z.xb, z.esz}, {py, z.yb, z.esz}, {cx, z.xb, z.esz}, {cy, z.yb, z.esz},
+                          {boundary, z.bd, sizeof(long long)}, {nodes, z.nd, 2 * sizeof(double)},
+                          {scores_device, z.sc, sizeof(double)}, {expect_device, z.sc, sizeof(double)},
+                          {g_expect_device, z.sc, sizeof(double)}, {g_score_device, z.sc, sizeof(double)}};
+    const SideBuf out[] = {{px_grad, z.xb, z.esz}, {py_grad, z.yb, z.esz}, {cgrads ? cx_grad : nullptr, z.xb, z.esz},
+                           {cgrads ? cy_grad : nullptr, z.yb, z.esz}};
+    if (side_bad_buffers(in, 10, out, 4)) return RNNT_STATUS_INVALID_VALUE;
     const ExpectCall c = {px, py, cx, cy, boundary, const_cast<void*>(scores_device), const_cast<void*>(expect_device), nullptr,
                           nullptr, const_cast<void*>(nodes), g_expect_device, g_score_device, px_grad, py_grad,
                           cgrads ? cx_grad : nullptr, cgrads ? cy_grad : nullptr, S, T, minibatch, modified != 0,

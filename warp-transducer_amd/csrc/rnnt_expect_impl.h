@@ -34,11 +34,7 @@ struct ExpectCall {
     int phases;
 };
 
-static inline bool ex_shape_ok(int S, int T, int N) {
-    if (S < 0 || T < 1 || N < 1 || S + 1 > kExMaxU) return false;
-    const unsigned long long nodes = static_cast<unsigned long long>(T + 1LL) * (S + 1LL);
-    return nodes < (1ull << 25) && nodes * N < (1ull << 32);
-}
+static inline bool ex_shape_ok(int S, int T, int N) { return side_lattice_ok(S, T, N, kExMaxU); }
 
 template <typename Tag, bool MOD>
 static bool launch_ex_fwd(const ExpectCall& c, double* scores, double* expect, long long stride) {

@@ -1,29 +1,26 @@
 // rnnt_expect_kernels.h -- the gfx950 kernels of the expected path cost over edge log-probabilities (include/rnnt_expect.h):
-// the expectation semiring on the lattice bestpath_sweep_kernel walks in max-plus, on the same schedule.
+// the expectation semiring on the px / py lattice.  The schedule of kernels 1 and 2 -- a block per sample, a thread per
+// lattice row, chunked prefetch, the neighbour's hand-over through DPP and LDS words -- is pxpy_sweep's (rnnt_pxpy.h);
+// what is here is each kernel's semiring, its stores and its fills.
 //
-//   1 expect_fwd_kernel       one block per sample, a thread per lattice row (row = s - s0).  Regular type: row r meets
-//                             t = t0 + d - r on anti-diagonal d; modified type: every row meets t = t0 + d.  A thread walks
-//                             ITS OWN rows px / py / cx / cy [b, s, :] in t order -- no transpose, no pack stage, no
-//                             workspace -- one chunk of kExChunk steps ahead of use.  The node's pair (a, A), the emit
-//                             candidate (a + px, A + cx) and the stay candidate (a + py, A + cy) are fp64 registers; the left
-//                             neighbour's emit candidate, a pair, arrives through four DPP moves (wave_shr1 on the halves)
-//                             inside a wavefront and through two LDS words per wavefront and step parity behind an LDS-only
-//                             barrier between wavefronts.  Per node: one exp and one log1p -- logaddexp with the share from
-//                             the same exponential -- and the convex combination, by select where a candidate is -inf.
-//                             Every node's pair goes to `nodes`; the block then writes (-inf, 0) outside the rectangle.
-//   2 expect_bwd_kernel       the mirrored schedule, steps in reverse: the thread of row r holds (bt, Bc) of its node in
-//                             registers, takes the right neighbour's pair through wave_shl1 / the LDS words, reads
-//                             nodes[u] a chunk ahead with the rows and stores the gradients of u's two out-edges as it
-//                             goes: no second table, no element-wise pass over a table.  occ_e = exp(a[u] + bt[u] - score)
-//                             times the edge's share of bt[u]: two exponentials and one log1p per node.  The block then
-//                             writes the zeros outside the rectangle's edges.
+//   1 expect_fwd_kernel       the sweep over px / py / cx / cy [b, s, :], kExChunk steps ahead of use.  The node's pair
+//                             (a, A) and the stay candidate (a + py, A + cy) are fp64 registers; the emit candidate
+//                             (a + px, A + cx) is the pair handed to the row above.  Per node: one exp and one log1p --
+//                             logaddexp with the share from the same exponential -- and the convex combination, by select
+//                             where a candidate is -inf.  Every node's pair goes to `nodes`; the block then writes
+//                             (-inf, 0) outside the rectangle.
+//   2 expect_bwd_kernel       the sweep in reverse: the thread of row r hands (bt, Bc) of its node to the row below, reads
+//                             nodes[u] a chunk (kExChunkBwd steps) ahead with the rows and stores the gradients of u's two
+//                             out-edges as it goes: no second table, no element-wise pass over a table.  occ_e =
+//                             exp(a[u] + bt[u] - score) times the edge's share of bt[u]: two exponentials and one log1p per
+//                             node.  The block then writes the zeros outside the rectangle's edges.
 //   3 expect_restore_kernel   the host-scores entry parks (score, expect) of sample b in nodes[b, 0, 0] -- the one array
 //                             there is -- and this puts the node's own pair back behind the copies.
 //
-// Loads are element-wise, as bestpath_sweep_kernel's (DESIGN.md 8p lists the modified type's packets as open).
+// DESIGN.md 8p lists the modified type's 16-byte packets as open.
 #pragma once
 
-#include "rnnt_bestpath_kernels.h"     // BpRect / bp_rect; through rnnt_kernels.h lds_barrier, cost_invalid, load1 / store1, wave_shr1
+#include "rnnt_pxpy.h"                 // PxRect / px_rect, pxpy_sweep; through rnnt_kernels.h cost_invalid, load1 / store1
 
 namespace rnnt {
 
@@ -63,10 +60,10 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void expect_fwd_kernel(
     __shared__ double edge[2][16][2];
     __shared__ double sh_score, sh_expect;
     __shared__ int sh_bad, sh_badc;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int nthreads = static_cast<int>(blockDim.x);
     const int TX = MOD ? T : T + 1, U = S + 1, T1 = T + 1;
-    const BpRect r = bp_rect(boundary, b, S, T);
+    const PxRect r = px_rect(boundary, b, S, T);
     const int s0 = r.s0, t0 = r.t0, Sr = r.Sr, Tr = r.Tr;
     const double NEG = -__builtin_huge_val(), INF = __builtin_huge_val();
     double2* nd = reinterpret_cast<double2*>(nodes) + static_cast<size_t>(b) * U * T1;
@@ -79,65 +76,32 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void expect_fwd_kernel(
         const size_t s = static_cast<size_t>(s0 + (hasy ? ls : 0));
         const size_t ox = (static_cast<size_t>(b) * S + (hasx ? s : 0)) * TX + t0;       // (never dereferenced unless hasx)
         const size_t oy = (static_cast<size_t>(b) * U + s) * T + t0;
-        const St *rx = px + ox, *ry = py + oy, *rcx = cx + ox, *rcy = cy + oy;
+        const St* const rx[2] = {px + ox, cx + ox};
+        const St* const ry[2] = {py + oy, cy + oy};
         double2* rn = nd + s * T1 + t0;
-        double stay_w = NEG, stay_c = 0.0, emit_w = NEG, emit_c = 0.0;
-        const int nsteps = MOD ? Tr + 1 : Tr + Sr + 1;
-        const int lastx = MOD ? Tr - 1 : Tr;                         // the last frame position with a symbol edge
+        double stay_w = NEG, stay_c = 0.0;                           // the stay candidate; the emit one is the hand-over
         bool bad = false, badc = false;
-        // steps d0 .. d0 + CH - 1 of the thread's row; an element outside the rectangle's edges is never read
-        auto load = [&](int d0, C (&wx)[CH], C (&wy)[CH], C (&kx)[CH], C (&ky)[CH]) {
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-                const int j = d0 + i - (MOD ? 0 : ls);
-                const bool ex = hasx && j >= 0 && j <= lastx, ey = hasy && j >= 0 && j < Tr;
-                wx[i] = ex ? load1<Tag>(rx + j) : C(0);
-                kx[i] = ex ? load1<Tag>(rcx + j) : C(0);
-                wy[i] = ey ? load1<Tag>(ry + j) : C(0);
-                ky[i] = ey ? load1<Tag>(rcy + j) : C(0);
-            }
-        };
-        C awx[CH], awy[CH], akx[CH], aky[CH], bwx[CH], bwy[CH], bkx[CH], bky[CH];
-        load(0, awx, awy, akx, aky);
-        // The two buffers keep FIXED roles per call site (the loop is unrolled by two chunks), as bestpath_sweep_kernel's.
-        auto chunk = [&](int d0, C (&wxs)[CH], C (&wys)[CH], C (&kxs)[CH], C (&kys)[CH], C (&nwx)[CH], C (&nwy)[CH],
-                         C (&nkx)[CH], C (&nky)[CH]) {
-            if (d0 + CH < nsteps) load(d0 + CH, nwx, nwy, nkx, nky);
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-                const int d = d0 + i;
-                if (d >= nsteps) break;
-                double left_w = wave_shr1(NEG, emit_w);              // lane 0 keeps -inf: row -1 is no row
-                double left_c = wave_shr1(0.0, emit_c);
-                if (MULTI) {
-                    if (lane == 63) { edge[d & 1][wave][0] = emit_w; edge[d & 1][wave][1] = emit_c; }
-                    lds_barrier();
-                    if (lane == 0 && wave > 0) { left_w = edge[d & 1][wave - 1][0]; left_c = edge[d & 1][wave - 1][1]; }
-                }
-                const int j = d - (MOD ? 0 : ls);
-                const bool act = hasy && j >= 0 && j <= Tr;
-                ExNode n = ex_combine(left_w, left_c, stay_w, stay_c);
+        const double none[2] = {NEG, 0.0};                           // row -1 is no row
+        pxpy_sweep<Tag, MOD, MULTI, false, 2, 2, CH, PxNoX>(
+            rx, ry, ls, Sr, Tr, edge, none, [](int, bool) { return PxNoX{}; },
+            [&](int j, bool act, bool ex, bool ey, const double (&left)[2], const C (&wxs)[2], const C (&wys)[2], PxNoX,
+                double (&emit)[2]) {
+                ExNode n = ex_combine(left[0], left[1], stay_w, stay_c);
                 if (ls == 0 && j == 0) { n.w = 0.0; n.c = 0.0; }     // the source (both candidates are -inf there)
-                const bool ex = act && hasx && j <= lastx, ey = act && j < Tr;
-                const double wx = static_cast<double>(wxs[i]), wy = static_cast<double>(wys[i]);
-                const double kx = static_cast<double>(kxs[i]), ky = static_cast<double>(kys[i]);
+                const double wx = static_cast<double>(wxs[0]), wy = static_cast<double>(wys[0]);
+                const double kx = static_cast<double>(wxs[1]), ky = static_cast<double>(wys[1]);
                 bad = bad || (ex && !(wx < INF)) || (ey && !(wy < INF));           // NaN or +inf on an edge of the rectangle
-                emit_w = ex ? n.w + wx : NEG;
+                emit[0] = ex ? n.w + wx : NEG;
                 stay_w = ey ? n.w + wy : NEG;
                 // a non-finite cost on a reachable edge of finite weight
-                badc = badc || (emit_w > NEG && !(__builtin_fabs(kx) < INF)) || (stay_w > NEG && !(__builtin_fabs(ky) < INF));
-                emit_c = emit_w > NEG ? n.c + kx : 0.0;
+                badc = badc || (emit[0] > NEG && !(__builtin_fabs(kx) < INF)) || (stay_w > NEG && !(__builtin_fabs(ky) < INF));
+                emit[1] = emit[0] > NEG ? n.c + kx : 0.0;
                 stay_c = stay_w > NEG ? n.c + ky : 0.0;
                 if (act) {
                     rn[j] = make_double2(n.w, n.c);
                     if (ls == Sr && j == Tr) { sh_score = n.w; sh_expect = n.c; }
                 }
-            }
-        };
-        for (int d0 = 0; d0 < nsteps; d0 += 2 * CH) {
-            chunk(d0, awx, awy, akx, aky, bwx, bwy, bkx, bky);
-            if (d0 + CH < nsteps) chunk(d0 + CH, bwx, bwy, bkx, bky, awx, awy, akx, aky);
-        }
+            });
         if (bad) sh_bad = 1;                                         // (several bad edges race: any store will do)
         if (badc) sh_badc = 1;
     }
@@ -175,10 +139,10 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void expect_bwd_kernel(
     using C = typename Tag::comp;
     constexpr int CH = ex_chunk<Tag>(kExChunkBwd);
     __shared__ double edge[2][16][2];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
-    const int nthreads = static_cast<int>(blockDim.x), nwaves = nthreads >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int nthreads = static_cast<int>(blockDim.x);
     const int TX = MOD ? T : T + 1, U = S + 1, T1 = T + 1;
-    const BpRect r = bp_rect(boundary, b, S, T);
+    const PxRect r = px_rect(boundary, b, S, T);
     const int s0 = r.s0, t0 = r.t0, Sr = r.Sr, Tr = r.Tr;
     const double NEG = -__builtin_huge_val();
     const double sc = scores[static_cast<size_t>(b) * stride], ec = expect[static_cast<size_t>(b) * stride];
@@ -193,53 +157,26 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void expect_bwd_kernel(
         const size_t s = static_cast<size_t>(s0 + (hasy ? ls : 0));
         const size_t ox = bx0 + (hasx ? s : 0) * TX + t0;                      // (never dereferenced unless hasx)
         const size_t oy = by0 + s * T + t0;
-        const St *rx = px + ox, *ry = py + oy, *rcx = cx + ox, *rcy = cy + oy;
+        const St* const rx[2] = {px + ox, cx + ox};
+        const St* const ry[2] = {py + oy, cy + oy};
         const double2* rn = reinterpret_cast<const double2*>(nodes) + (static_cast<size_t>(b) * U + s) * T1 + t0;
-        double own_w = NEG, own_c = 0.0;                                       // (bt, Bc) of the row's node of the step before
-        const int nsteps = MOD ? Tr + 1 : Tr + Sr + 1;
-        // reverse steps e0 .. e0 + CH - 1 (step d = nsteps - 1 - e) of the thread's row, and the node pairs
-        auto load = [&](int e0, C (&wx)[CH], C (&wy)[CH], C (&kx)[CH], C (&ky)[CH], double2 (&nn)[CH]) {
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-                const int j = nsteps - 1 - (e0 + i) - (MOD ? 0 : ls);
-                const bool ex = hasx && j >= 0 && j <= lastx, ey = hasy && j >= 0 && j < Tr;
-                wx[i] = ex ? load1<Tag>(rx + j) : C(0);
-                kx[i] = ex ? load1<Tag>(rcx + j) : C(0);
-                wy[i] = ey ? load1<Tag>(ry + j) : C(0);
-                ky[i] = ey ? load1<Tag>(rcy + j) : C(0);
-                nn[i] = (hasy && j >= 0 && j <= Tr && !(ls == 0 && j == 0)) ? rn[j] : make_double2(0.0, 0.0);
-            }
-        };
-        C awx[CH], awy[CH], akx[CH], aky[CH], bwx[CH], bwy[CH], bkx[CH], bky[CH];
-        double2 an[CH], bn[CH];
-        load(0, awx, awy, akx, aky, an);
-        auto chunk = [&](int e0, C (&wxs)[CH], C (&wys)[CH], C (&kxs)[CH], C (&kys)[CH], double2 (&nns)[CH], C (&nwx)[CH],
-                         C (&nwy)[CH], C (&nkx)[CH], C (&nky)[CH], double2 (&nnn)[CH]) {
-            if (e0 + CH < nsteps) load(e0 + CH, nwx, nwy, nkx, nky, nnn);
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-                const int e = e0 + i;
-                if (e >= nsteps) break;
-                double right_w = wave_shl1(NEG, own_w);              // lane 63 keeps -inf
-                double right_c = wave_shl1(0.0, own_c);
-                if (MULTI) {
-                    if (lane == 0) { edge[e & 1][wave][0] = own_w; edge[e & 1][wave][1] = own_c; }
-                    lds_barrier();
-                    if (lane == 63 && wave + 1 < nwaves) { right_w = edge[e & 1][wave + 1][0]; right_c = edge[e & 1][wave + 1][1]; }
-                }
-                const int j = nsteps - 1 - e - (MOD ? 0 : ls);
-                const bool act = hasy && j >= 0 && j <= Tr;
-                const bool ex = act && hasx && j <= lastx, ey = act && j < Tr;
-                const double kx = static_cast<double>(kxs[i]), ky = static_cast<double>(kys[i]);
-                const double x = ex ? static_cast<double>(wxs[i]) + right_w : NEG;
-                const double y = ey ? static_cast<double>(wys[i]) + own_w : NEG;
-                const double xc = x > NEG ? kx + right_c : 0.0, yc = y > NEG ? ky + own_c : 0.0;
+        const double none[2] = {NEG, 0.0};                           // the row past the last is no row
+        // the hand-over `own` is (bt, Bc) of the row's node; x: the node's forward pair, read a chunk ahead with the edges
+        pxpy_sweep<Tag, MOD, MULTI, true, 2, 2, CH, double2>(
+            rx, ry, ls, Sr, Tr, edge, none,
+            [&](int j, bool in) { return (in && !(ls == 0 && j == 0)) ? rn[j] : make_double2(0.0, 0.0); },   // the source: (0, 0)
+            [&](int j, bool act, bool ex, bool ey, const double (&right)[2], const C (&wxs)[2], const C (&wys)[2],
+                const double2& nn, double (&own)[2]) {
+                const double kx = static_cast<double>(wxs[1]), ky = static_cast<double>(wys[1]);
+                const double x = ex ? static_cast<double>(wxs[0]) + right[0] : NEG;
+                const double y = ey ? static_cast<double>(wys[0]) + own[0] : NEG;
+                const double xc = x > NEG ? kx + right[1] : 0.0, yc = y > NEG ? ky + own[1] : 0.0;
                 ExNode n = ex_combine(x, xc, y, yc);
                 if (ls == Sr && j == Tr) { n.w = 0.0; n.c = 0.0; }   // the sink (no out-edge: both candidates are -inf)
-                own_w = act ? n.w : NEG;
-                own_c = act ? n.c : 0.0;
+                own[0] = act ? n.w : NEG;
+                own[1] = act ? n.c : 0.0;
                 if (act) {
-                    const double a = nns[i].x, A = nns[i].y;         // the source: (0, 0)
+                    const double a = nn.x, A = nn.y;
                     const double occ = exp(a + n.w - sc);            // the node's occupation; -inf - ... = -inf: 0
                     const double occx = x > NEG ? occ * n.share : 0.0, occy = y > NEG ? occ * (1.0 - n.share) : 0.0;
                     if (ex) {
@@ -253,12 +190,7 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void expect_bwd_kernel(
                         if (WITH_COST_GRADS) store1<Tag>(cy_grad + oy + j, static_cast<C>(occy > 0.0 ? ge * occy : 0.0));
                     }
                 }
-            }
-        };
-        for (int e0 = 0; e0 < nsteps; e0 += 2 * CH) {
-            chunk(e0, awx, awy, akx, aky, an, bwx, bwy, bkx, bky, bn);
-            if (e0 + CH < nsteps) chunk(e0 + CH, bwx, bwy, bkx, bky, bn, awx, awy, akx, aky, an);
-        }
+            });
     }
 
     // ---- everything the sweep did not write: zeros outside the rectangle's edges; without a path zeros (NaN score: NaN) inside
@@ -285,7 +217,7 @@ __global__ __launch_bounds__(256) void expect_restore_kernel(const long long* __
                                                              int T, int B) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
-    const BpRect r = bp_rect(boundary, b, S, T);
+    const PxRect r = px_rect(boundary, b, S, T);
     double2* nd = reinterpret_cast<double2*>(nodes) + static_cast<size_t>(b) * (S + 1) * (T + 1);
     nd[0] = make_double2((r.ok && r.s0 == 0 && r.t0 == 0) ? 0.0 : -__builtin_huge_val(), 0.0);
 }

@@ -29,6 +29,7 @@
 #pragma once
 
 #include "rnnt_ar_kernels.h"           // stage 2: both lattices; through it mono_lse2, tdt_cell, the record format
+#include "rnnt_pxpy.h"                 // PxRect / px_rect: the rectangle of a sample
 
 namespace rnnt {
 
@@ -64,14 +65,9 @@ __global__ __launch_bounds__(256) void mi_pack_kernel(
     __shared__ C wb[kMiTile][kMiTile + 1], wl[kMiTile][kMiTile + 1];
     const int b = b0 + blockIdx.y, tid = threadIdx.x;
     const int tu = blockIdx.x % tiles_u, tt = blockIdx.x / tiles_u;
-    long long q0 = 0, r0 = 0, q1 = S, r1 = T;
-    if (boundary != nullptr) {
-        const long long* bd = boundary + static_cast<size_t>(b) * 4;
-        q0 = bd[0]; r0 = bd[1]; q1 = bd[2]; r1 = bd[3];
-    }
-    const bool ok = 0 <= q0 && q0 <= q1 && q1 <= S && 0 <= r0 && r0 <= r1 && r1 <= T;
-    const int s0 = ok ? static_cast<int>(q0) : 0, t0 = ok ? static_cast<int>(r0) : 0;
-    const int Sr = ok ? static_cast<int>(q1 - q0) : -1, Tr = ok ? static_cast<int>(r1 - r0) : 0;
+    const PxRect rc = px_rect(boundary, b, S, T);
+    const int s0 = rc.s0, t0 = rc.t0, Sr = rc.Sr, Tr = rc.Tr;
+    const bool ok = rc.ok;
     const int Tn = ok ? (MOD ? Tr : Tr + 1) : 0;                     // node columns with out-edges
     if (blockIdx.x == 0 && tid == 0) {
         xlen[b] = Tn;

@@ -11,25 +11,6 @@ using namespace rnnt;
 
 namespace {
 
-// A buffer of a call: [p, p + bytes), `elem` the size its address must be a multiple of; p == nullptr: not given.
-struct RgBuf { const void* p; unsigned long long bytes, elem; };
-
-bool rg_overlap(const RgBuf& a, const RgBuf& b) {
-    if (a.p == nullptr || b.p == nullptr || a.bytes == 0 || b.bytes == 0) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
-    return x < y + b.bytes && y < x + a.bytes;
-}
-
-// Every buffer on an element boundary; the output sharing no byte with an input (inputs may alias inputs).  true: refused.
-bool rg_bad_buffers(const RgBuf* in, int nin, const RgBuf& out) {
-    if (reinterpret_cast<uintptr_t>(out.p) % out.elem != 0) return true;
-    for (int i = 0; i < nin; ++i) {
-        if (in[i].p != nullptr && reinterpret_cast<uintptr_t>(in[i].p) % in[i].elem != 0) return true;
-        if (rg_overlap(out, in[i])) return true;
-    }
-    return false;
-}
-
 bool rg_bad_common(const void* px, const void* py, int S, int T, int N, int R, const rnntOptions& o, int dtype_code) {
     return !rg_shape_ok(S, T, N) || dtype_code < 0 || dtype_code > 3 || loc_of(o) != RNNT_GPU || R < 1 || R > S + 1 ||
            py == nullptr || (S > 0 && px == nullptr);
@@ -55,8 +36,9 @@ rnntStatus_t compute_rnnt_prune_ranges_occ(const void* px_grad, const void* py_g
         step > (R - 1 > 1 ? R - 1 : 1))
         return RNNT_STATUS_INVALID_VALUE;
     const RgSizes z = rg_sizes(S, T, minibatch, modified, dtype_code);
-    const RgBuf in[] = {{S > 0 ? px_grad : nullptr, z.xb, z.esz}, {py_grad, z.yb, z.esz}, {boundary, z.bd, sizeof(long long)}};
-    if (rg_bad_buffers(in, 3, {ranges, z.rg, sizeof(int)})) return RNNT_STATUS_INVALID_VALUE;
+    const SideBuf in[] = {{S > 0 ? px_grad : nullptr, z.xb, z.esz}, {py_grad, z.yb, z.esz}, {boundary, z.bd, sizeof(long long)}};
+    const SideBuf out = {ranges, z.rg, sizeof(int)};
+    if (side_bad_buffers(in, 3, &out, 1)) return RNNT_STATUS_INVALID_VALUE;
     const RangesCall c = {px_grad, py_grad, boundary, ranges, nullptr, S, T, minibatch, R, step, modified != 0,
                           reinterpret_cast<hipStream_t>(options.stream)};
     return side_dispatch(dtype_code, [&](auto tag) { return run_ranges<decltype(tag)>(c); });
@@ -68,9 +50,10 @@ rnntStatus_t compute_rnnt_range_coverage(const void* px_grad, const void* py_gra
     if (rg_bad_common(px_grad, py_grad, S, T, minibatch, R, options, dtype_code) || ranges == nullptr || kept == nullptr)
         return RNNT_STATUS_INVALID_VALUE;
     const RgSizes z = rg_sizes(S, T, minibatch, modified, dtype_code);
-    const RgBuf in[] = {{S > 0 ? px_grad : nullptr, z.xb, z.esz}, {py_grad, z.yb, z.esz}, {boundary, z.bd, sizeof(long long)},
-                        {ranges, z.rg, sizeof(int)}};
-    if (rg_bad_buffers(in, 4, {kept, z.kp, sizeof(double)})) return RNNT_STATUS_INVALID_VALUE;
+    const SideBuf in[] = {{S > 0 ? px_grad : nullptr, z.xb, z.esz}, {py_grad, z.yb, z.esz}, {boundary, z.bd, sizeof(long long)},
+                          {ranges, z.rg, sizeof(int)}};
+    const SideBuf out = {kept, z.kp, sizeof(double)};
+    if (side_bad_buffers(in, 4, &out, 1)) return RNNT_STATUS_INVALID_VALUE;
     const RangesCall c = {px_grad, py_grad, boundary, const_cast<int*>(ranges), kept, S, T, minibatch, R, 1, modified != 0,
                           reinterpret_cast<hipStream_t>(options.stream)};
     return side_dispatch(dtype_code, [&](auto tag) { return run_ranges<decltype(tag)>(c); });

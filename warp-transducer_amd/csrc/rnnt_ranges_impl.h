@@ -29,11 +29,7 @@ struct RangesCall {
     hipStream_t stream;
 };
 
-static inline bool rg_shape_ok(int S, int T, int N) {
-    if (S < 0 || T < 1 || N < 1 || S + 1 > kRgMaxU) return false;
-    const unsigned long long nodes = static_cast<unsigned long long>(T + 1LL) * (S + 1LL);
-    return nodes < (1ull << 25) && nodes * N < (1ull << 32);
-}
+static inline bool rg_shape_ok(int S, int T, int N) { return side_lattice_ok(S, T, N, kRgMaxU); }
 
 template <typename Tag, bool MOD>
 static rnntStatus_t run_ranges_type(const RangesCall& c) {

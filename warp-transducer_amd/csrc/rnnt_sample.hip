@@ -11,30 +11,6 @@ using namespace rnnt;
 
 namespace {
 
-// A buffer of a call: [p, p + bytes), `elem` the size its address must be a multiple of; p == nullptr: not given.
-struct SaBuf { const void* p; unsigned long long bytes, elem; };
-
-bool sa_overlap(const SaBuf& a, const SaBuf& b) {
-    if (a.p == nullptr || b.p == nullptr || a.bytes == 0 || b.bytes == 0) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
-    return x < y + b.bytes && y < x + a.bytes;
-}
-
-// Every buffer on an element boundary; no output sharing a byte with an input or another output (inputs may alias
-// inputs).  true: refused.
-bool sa_bad_buffers(const SaBuf* in, int nin, const SaBuf* out, int nout) {
-    for (int i = 0; i < nin; ++i)
-        if (in[i].p != nullptr && reinterpret_cast<uintptr_t>(in[i].p) % in[i].elem != 0) return true;
-    for (int i = 0; i < nout; ++i) {
-        if (out[i].p != nullptr && reinterpret_cast<uintptr_t>(out[i].p) % out[i].elem != 0) return true;
-        for (int j = 0; j < nin; ++j)
-            if (sa_overlap(out[i], in[j])) return true;
-        for (int j = i + 1; j < nout; ++j)
-            if (sa_overlap(out[i], out[j])) return true;
-    }
-    return false;
-}
-
 bool sa_bad_common(int S, int T, int N, int K, const rnntOptions& o, int dtype_code) {
     return !sa_shape_ok(S, T, N, K) || dtype_code < 0 || dtype_code > 3 || loc_of(o) != RNNT_GPU;
 }
@@ -61,11 +37,11 @@ rnntStatus_t compute_rnnt_sample(const void* px, const void* py, const void* bou
         return RNNT_STATUS_INVALID_VALUE;
     const SaSizes z = sa_sizes(S, T, minibatch, K, modified, dtype_code);
     const bool sym = S > 0;
-    const SaBuf in[] = {{sym ? px : nullptr, z.xb, z.esz}, {py, z.yb, z.esz}, {boundary, z.bd, sizeof(long long)},
-                        {sym ? uniforms : nullptr, z.un, sizeof(float)}};
-    const SaBuf out[] = {{scores, z.sc, sizeof(double)}, {alpha, z.al, sizeof(double)},
-                         {sym ? frames : nullptr, z.fr, sizeof(int)}, {weights, z.wk, sizeof(double)}};
-    if (sa_bad_buffers(in, 4, out, 4)) return RNNT_STATUS_INVALID_VALUE;
+    const SideBuf in[] = {{sym ? px : nullptr, z.xb, z.esz}, {py, z.yb, z.esz}, {boundary, z.bd, sizeof(long long)},
+                          {sym ? uniforms : nullptr, z.un, sizeof(float)}};
+    const SideBuf out[] = {{scores, z.sc, sizeof(double)}, {alpha, z.al, sizeof(double)},
+                           {sym ? frames : nullptr, z.fr, sizeof(int)}, {weights, z.wk, sizeof(double)}};
+    if (side_bad_buffers(in, 4, out, 4)) return RNNT_STATUS_INVALID_VALUE;
     const SampleCall c = {px, py, boundary, uniforms, nullptr, scores, alpha, frames, weights, nullptr, nullptr, S, T,
                           minibatch, K, modified != 0, reinterpret_cast<hipStream_t>(options.stream), 3};
     return side_dispatch(dtype_code, [&](auto tag) { return run_sample<decltype(tag)>(c); });
@@ -79,11 +55,11 @@ rnntStatus_t compute_rnnt_sample_walk(const void* px, const void* py, const void
         return RNNT_STATUS_INVALID_VALUE;
     const SaSizes z = sa_sizes(S, T, minibatch, K, modified, dtype_code);
     const bool sym = S > 0;
-    const SaBuf in[] = {{sym ? px : nullptr, z.xb, z.esz}, {py, z.yb, z.esz}, {boundary, z.bd, sizeof(long long)},
-                        {sym ? uniforms : nullptr, z.un, sizeof(float)}, {alpha, z.al, sizeof(double)},
-                        {scores_device, z.sc, sizeof(double)}};
-    const SaBuf out[] = {{sym ? frames : nullptr, z.fr, sizeof(int)}, {weights, z.wk, sizeof(double)}};
-    if (sa_bad_buffers(in, 6, out, 2)) return RNNT_STATUS_INVALID_VALUE;
+    const SideBuf in[] = {{sym ? px : nullptr, z.xb, z.esz}, {py, z.yb, z.esz}, {boundary, z.bd, sizeof(long long)},
+                          {sym ? uniforms : nullptr, z.un, sizeof(float)}, {alpha, z.al, sizeof(double)},
+                          {scores_device, z.sc, sizeof(double)}};
+    const SideBuf out[] = {{sym ? frames : nullptr, z.fr, sizeof(int)}, {weights, z.wk, sizeof(double)}};
+    if (side_bad_buffers(in, 6, out, 2)) return RNNT_STATUS_INVALID_VALUE;
     const SampleCall c = {px, py, boundary, uniforms, nullptr, const_cast<void*>(scores_device), const_cast<void*>(alpha),
                           frames, weights, nullptr, nullptr, S, T, minibatch, K, modified != 0,
                           reinterpret_cast<hipStream_t>(options.stream), 2};
@@ -98,10 +74,10 @@ rnntStatus_t compute_rnnt_path_weights(const void* px, const void* py, const voi
         return RNNT_STATUS_INVALID_VALUE;
     const SaSizes z = sa_sizes(S, T, minibatch, K, modified, dtype_code);
     const bool sym = S > 0;
-    const SaBuf in[] = {{sym ? px : nullptr, z.xb, z.esz}, {py, z.yb, z.esz}, {boundary, z.bd, sizeof(long long)},
-                        {sym ? frames : nullptr, z.fr, sizeof(int)}};
-    const SaBuf out[] = {{weights, z.wk, sizeof(double)}};
-    if (sa_bad_buffers(in, 4, out, 1)) return RNNT_STATUS_INVALID_VALUE;
+    const SideBuf in[] = {{sym ? px : nullptr, z.xb, z.esz}, {py, z.yb, z.esz}, {boundary, z.bd, sizeof(long long)},
+                          {sym ? frames : nullptr, z.fr, sizeof(int)}};
+    const SideBuf out[] = {{weights, z.wk, sizeof(double)}};
+    if (side_bad_buffers(in, 4, out, 1)) return RNNT_STATUS_INVALID_VALUE;
     const SampleCall c = {px, py, boundary, nullptr, nullptr, nullptr, nullptr, const_cast<int*>(frames), weights, nullptr,
                           nullptr, S, T, minibatch, K, modified != 0, reinterpret_cast<hipStream_t>(options.stream), 4};
     return side_dispatch(dtype_code, [&](auto tag) { return run_sample<decltype(tag)>(c); });
@@ -114,10 +90,10 @@ rnntStatus_t compute_rnnt_path_edges(const int* frames, const void* coeff, const
         return RNNT_STATUS_INVALID_VALUE;
     const SaSizes z = sa_sizes(S, T, minibatch, K, modified, dtype_code);
     const bool sym = S > 0;
-    const SaBuf in[] = {{sym ? frames : nullptr, z.fr, sizeof(int)}, {coeff, z.wk, sizeof(double)},
-                        {boundary, z.bd, sizeof(long long)}};
-    const SaBuf out[] = {{sym ? px_acc : nullptr, z.xb, z.esz}, {py_acc, z.yb, z.esz}};
-    if (sa_bad_buffers(in, 3, out, 2)) return RNNT_STATUS_INVALID_VALUE;
+    const SideBuf in[] = {{sym ? frames : nullptr, z.fr, sizeof(int)}, {coeff, z.wk, sizeof(double)},
+                          {boundary, z.bd, sizeof(long long)}};
+    const SideBuf out[] = {{sym ? px_acc : nullptr, z.xb, z.esz}, {py_acc, z.yb, z.esz}};
+    if (side_bad_buffers(in, 3, out, 2)) return RNNT_STATUS_INVALID_VALUE;
     const SampleCall c = {nullptr, nullptr, boundary, nullptr, coeff, nullptr, nullptr, const_cast<int*>(frames), nullptr,
                           px_acc, py_acc, S, T, minibatch, K, modified != 0, reinterpret_cast<hipStream_t>(options.stream), 8};
     return side_dispatch(dtype_code, [&](auto tag) { return run_sample<decltype(tag)>(c); });

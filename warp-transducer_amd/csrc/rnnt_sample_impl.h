@@ -34,9 +34,7 @@ struct SampleCall {
 };
 
 static inline bool sa_shape_ok(int S, int T, int N, int K) {
-    if (S < 0 || T < 1 || N < 1 || S + 1 > kSaMaxU || K < 1 || K > kSaMaxK) return false;
-    const unsigned long long nodes = static_cast<unsigned long long>(T + 1LL) * (S + 1LL);
-    if (!(nodes < (1ull << 25) && nodes * N < (1ull << 32))) return false;
+    if (!side_lattice_ok(S, T, N, kSaMaxU) || K < 1 || K > kSaMaxK) return false;
     return static_cast<unsigned long long>(N) * K * (S > 1 ? S : 1) < (1ull << 31);
 }
 

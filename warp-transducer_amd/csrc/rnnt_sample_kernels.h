@@ -1,15 +1,11 @@
 // rnnt_sample_kernels.h -- the gfx950 kernels of the alignment sampler over edge log-probabilities (include/rnnt_sample.h):
-// the log-sum sweep on the lattice expect_fwd_kernel walks with a pair per node, and the walks back from the terminal.
+// the log-sum sweep on the px / py lattice, and the walks back from the terminal.
 //
-//   1 sample_fwd_kernel       expect_fwd_kernel's schedule with ONE double per node: a block per sample, a thread per
-//                             lattice row (row = s - s0); regular type: row r meets t = t0 + d - r on anti-diagonal d,
-//                             modified type: every row meets t = t0 + d.  A thread reads ITS OWN rows px / py [b, s, :] a
-//                             chunk of kSaChunk steps ahead of use, in two register buffers with fixed roles.  The left
-//                             neighbour's emit candidate arrives through two DPP moves (wave_shr1) inside a wavefront and
-//                             through one LDS word per wavefront and step parity behind an LDS-only barrier between
-//                             wavefronts.  Per node one exp and one log1p; a -inf candidate is selected out.  Every
-//                             node's value goes to `alpha`; the block then writes -inf outside the rectangle and the
-//                             score last.
+//   1 sample_fwd_kernel       pxpy_sweep (rnnt_pxpy.h: a block per sample, a thread per lattice row, chunked prefetch, the
+//                             neighbour's hand-over through DPP and LDS words) with ONE double per node, px / py [b, s, :]
+//                             kSaChunk steps ahead of use.  The emit candidate is the value handed to the row above.  Per
+//                             node one exp and one log1p; a -inf candidate is selected out.  Every node's value goes to
+//                             `alpha`; the block then writes -inf outside the rectangle and the score last.
 //   2 sample_walk_kernel      a thread per walk (b, k); the walks of one sample sit in the same wavefronts.  A step
 //                             issues the loads of alpha[s - 1, t'], px[s - 1, t'], alpha[s, t - 1], py[s, t - 1] and the
 //                             uniform together: ONE dependent round trip per step.  Whichever edge is taken, the
@@ -20,11 +16,9 @@
 //   4 path_edges_kernel       a block per (sample, slice of rows): the threads first judge the K rows of frames (valid or
 //                             not, LDS), then a thread per output element loops over k in ascending order with two
 //                             comparisons against the interval read from frames.  No atomics.
-//
-// Loads are element-wise, as expect_fwd_kernel's.
 #pragma once
 
-#include "rnnt_bestpath_kernels.h"     // BpRect / bp_rect; through rnnt_kernels.h lds_barrier, cost_invalid, load1 / store1, wave_shr1
+#include "rnnt_pxpy.h"                 // PxRect / px_rect, pxpy_sweep; through rnnt_kernels.h cost_invalid, load1 / store1
 
 namespace rnnt {
 
@@ -73,13 +67,13 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void sample_fwd_kernel(
     using St = typename Tag::store;
     using C = typename Tag::comp;
     constexpr int CH = sa_chunk<Tag>();
-    __shared__ double edge[2][16];
+    __shared__ double edge[2][16][1];
     __shared__ double sh_score;
     __shared__ int sh_bad;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int nthreads = static_cast<int>(blockDim.x);
     const int TX = MOD ? T : T + 1, U = S + 1, T1 = T + 1;
-    const BpRect r = bp_rect(boundary, b, S, T);
+    const PxRect r = px_rect(boundary, b, S, T);
     const int s0 = r.s0, t0 = r.t0, Sr = r.Sr, Tr = r.Tr;
     const double NEG = -__builtin_huge_val(), INF = __builtin_huge_val();
     double* al = alpha + static_cast<size_t>(b) * U * T1;
@@ -92,56 +86,27 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void sample_fwd_kernel(
         const size_t s = static_cast<size_t>(s0 + (hasy ? ls : 0));
         const size_t ox = (static_cast<size_t>(b) * S + (hasx ? s : 0)) * TX + t0;       // (never dereferenced unless hasx)
         const size_t oy = (static_cast<size_t>(b) * U + s) * T + t0;
-        const St *rx = px + ox, *ry = py + oy;
+        const St* const rx[1] = {px + ox};
+        const St* const ry[1] = {py + oy};
         double* rn = al + s * T1 + t0;
-        double stay = NEG, emit = NEG;
-        const int nsteps = MOD ? Tr + 1 : Tr + Sr + 1;
-        const int lastx = MOD ? Tr - 1 : Tr;                         // the last frame position with a symbol edge
+        double stay = NEG;                                           // the stay candidate; the emit one is the hand-over
         bool bad = false;
-        // steps d0 .. d0 + CH - 1 of the thread's row; an element outside the rectangle's edges is never read
-        auto load = [&](int d0, C (&wx)[CH], C (&wy)[CH]) {
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-                const int j = d0 + i - (MOD ? 0 : ls);
-                const bool ex = hasx && j >= 0 && j <= lastx, ey = hasy && j >= 0 && j < Tr;
-                wx[i] = ex ? load1<Tag>(rx + j) : C(0);
-                wy[i] = ey ? load1<Tag>(ry + j) : C(0);
-            }
-        };
-        C awx[CH], awy[CH], bwx[CH], bwy[CH];
-        load(0, awx, awy);
-        // The two buffers keep FIXED roles per call site (the loop is unrolled by two chunks), as expect_fwd_kernel's.
-        auto chunk = [&](int d0, C (&wxs)[CH], C (&wys)[CH], C (&nwx)[CH], C (&nwy)[CH]) {
-            if (d0 + CH < nsteps) load(d0 + CH, nwx, nwy);
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-                const int d = d0 + i;
-                if (d >= nsteps) break;
-                double left = wave_shr1(NEG, emit);                  // lane 0 keeps -inf: row -1 is no row
-                if (MULTI) {
-                    if (lane == 63) edge[d & 1][wave] = emit;
-                    lds_barrier();
-                    if (lane == 0 && wave > 0) left = edge[d & 1][wave - 1];
-                }
-                const int j = d - (MOD ? 0 : ls);
-                const bool act = hasy && j >= 0 && j <= Tr;
-                double a = sa_logaddexp(left, stay);
+        const double none[1] = {NEG};                                // row -1 is no row
+        pxpy_sweep<Tag, MOD, MULTI, false, 1, 1, CH, PxNoX>(
+            rx, ry, ls, Sr, Tr, edge, none, [](int, bool) { return PxNoX{}; },
+            [&](int j, bool act, bool ex, bool ey, const double (&left)[1], const C (&wxs)[1], const C (&wys)[1], PxNoX,
+                double (&emit)[1]) {
+                double a = sa_logaddexp(left[0], stay);
                 if (ls == 0 && j == 0) a = 0.0;                      // the source (both candidates are -inf there)
-                const bool ex = act && hasx && j <= lastx, ey = act && j < Tr;
-                const double wx = static_cast<double>(wxs[i]), wy = static_cast<double>(wys[i]);
+                const double wx = static_cast<double>(wxs[0]), wy = static_cast<double>(wys[0]);
                 bad = bad || (ex && !(wx < INF)) || (ey && !(wy < INF));           // NaN or +inf on an edge of the rectangle
-                emit = ex ? a + wx : NEG;
+                emit[0] = ex ? a + wx : NEG;
                 stay = ey ? a + wy : NEG;
                 if (act) {
                     rn[j] = a;
                     if (ls == Sr && j == Tr) sh_score = a;
                 }
-            }
-        };
-        for (int d0 = 0; d0 < nsteps; d0 += 2 * CH) {
-            chunk(d0, awx, awy, bwx, bwy);
-            if (d0 + CH < nsteps) chunk(d0 + CH, bwx, bwy, awx, awy);
-        }
+            });
         if (bad) sh_bad = 1;                                         // (several bad edges race: any store will do)
     }
     __threadfence_block();
@@ -165,7 +130,7 @@ __global__ __launch_bounds__(kSaWalkBlock) void sample_walk_kernel(
     const int b = blockIdx.x, k = blockIdx.y * static_cast<int>(blockDim.x) + threadIdx.x;
     if (k >= K) return;
     const int TX = MOD ? T : T + 1, U = S + 1, T1 = T + 1;
-    const BpRect r = bp_rect(boundary, b, S, T);
+    const PxRect r = px_rect(boundary, b, S, T);
     const int s0 = r.s0, t0 = r.t0, s1 = r.s0 + r.Sr, t1 = r.t0 + r.Tr;
     const double NEG = -__builtin_huge_val();
     const double sc = scores[b];
@@ -246,7 +211,7 @@ __global__ __launch_bounds__(64) void path_weights_kernel(
     const int TX = MOD ? T : T + 1, U = S + 1;
     for (long long q = blockIdx.x; q < BK; q += gridDim.x) {
         const int b = static_cast<int>(q / K);
-        const BpRect r = bp_rect(boundary, b, S, T);
+        const PxRect r = px_rect(boundary, b, S, T);
         const int s0 = r.s0, t0 = r.t0, s1 = r.s0 + r.Sr, t1 = r.t0 + r.Tr;
         const int* fr = frames + static_cast<size_t>(q) * S;
         const St* bx = px + static_cast<size_t>(b) * S * TX;
@@ -284,7 +249,7 @@ __global__ __launch_bounds__(kSaEdgeBlock) void path_edges_kernel(
     __shared__ unsigned char live[kSaMaxK];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int TX = MOD ? T : T + 1, U = S + 1;
-    const BpRect r = bp_rect(boundary, b, S, T);
+    const PxRect r = px_rect(boundary, b, S, T);
     const int s0 = r.s0, t0 = r.t0, s1 = r.s0 + r.Sr, t1 = r.t0 + r.Tr;
     const int* fb = frames + static_cast<size_t>(b) * K * S;
     for (int k = tid; k < K; k += kSaEdgeBlock) {

@@ -1,8 +1,9 @@
 // rnnt_side_host.h -- what the host drivers of the side libraries share on top of rnnt_host.h (the four losses -- pruned,
 // TDT, HAT, multi-blank -- all of it; the TDT alignment the dtype switch, the cell table and the launch arithmetic): the
 // call record their C entry points fill (SideCall), the dtype switch (side_dispatch), the buffer checks of every run_X
-// (side_buffers_ok), the cell-table workspace of TDT and multi-blank, and the launch arithmetic of the statistics and
-// gradient launchers.  Host code only: no kernel is named here, so a library's code objects hold exactly the kernels its
+// (side_buffers_ok), the buffer and lattice-size checks of the px / py libraries' C entries (SideBuf, side_bad_buffers,
+// side_lattice_ok: bestpath, expect, sample, ranges), the cell-table workspace of TDT and multi-blank, and the launch
+// arithmetic of the statistics and gradient launchers.  Host code only: no kernel is named here, so a library's code objects hold exactly the kernels its
 // own rnnt_X_impl.h launches.
 #pragma once
 #include "rnnt_host.h"
@@ -49,6 +50,40 @@ static inline bool side_buffers_ok(const SideCall& c, size_t elem_size, unsigned
     if (pa % elem_size != 0 || (c.grads != nullptr && pg % elem_size != 0)) return false;
     if (do_bwd && pg != pa && (pg > pa ? pg - pa : pa - pg) < elems * elem_size) return false;
     return true;
+}
+
+// ----------------------------------------------------------------------------- the px / py libraries' checks
+// (bestpath, expect, sample, ranges: no call record in common, no workspace; every array is an argument of its own)
+// A buffer of a call: [p, p + bytes), `elem` the size its address must be a multiple of; p == nullptr: not given.
+struct SideBuf { const void* p; unsigned long long bytes, elem; };
+
+static inline bool side_overlap(const SideBuf& a, const SideBuf& b) {
+    if (a.p == nullptr || b.p == nullptr || a.bytes == 0 || b.bytes == 0) return false;
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
+    return x < y + b.bytes && y < x + a.bytes;
+}
+
+// Every given buffer on an element boundary; no output sharing a byte with an input or another output (inputs may alias
+// inputs).  true: refused.
+static inline bool side_bad_buffers(const SideBuf* in, int nin, const SideBuf* out, int nout) {
+    for (int i = 0; i < nin; ++i)
+        if (in[i].p != nullptr && reinterpret_cast<uintptr_t>(in[i].p) % in[i].elem != 0) return true;
+    for (int i = 0; i < nout; ++i) {
+        if (out[i].p != nullptr && reinterpret_cast<uintptr_t>(out[i].p) % out[i].elem != 0) return true;
+        for (int j = 0; j < nin; ++j)
+            if (side_overlap(out[i], in[j])) return true;
+        for (int j = i + 1; j < nout; ++j)
+            if (side_overlap(out[i], out[j])) return true;
+    }
+    return false;
+}
+
+// The LIMITS of include/rnnt_{bestpath,expect,sample,ranges}.h on the lattice of a (B, S, T) call: S + 1 <= maxU,
+// (T + 1) (S + 1) < 2^25, B (T + 1) (S + 1) < 2^32.
+static inline bool side_lattice_ok(int S, int T, int N, int maxU) {
+    if (S < 0 || T < 1 || N < 1 || S + 1 > maxU) return false;
+    const unsigned long long nodes = static_cast<unsigned long long>(T + 1LL) * (S + 1LL);
+    return nodes < (1ull << 25) && nodes * N < (1ull << 32);
 }
 
 // ----------------------------------------------------------------------------- entry points
