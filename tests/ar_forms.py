@@ -10,7 +10,7 @@ import numpy as np
 
 from tests import ar_ref as R
 from tests import forms_common as C
-from tests.forms_common import STORES, object_of                        # noqa: F401  (this table's names)
+from tests.forms_common import STORES, object_of, stats_group           # noqa: F401  (this table's names)
 
 OBJECTS = {"f32": "rnnt_ar.hip", "f64": "rnnt_ar_f64.hip", "h16": "rnnt_ar_h16.hip"}
 STAGES = ("bounds", "stats", "lattice", "coef", "grad")
@@ -24,11 +24,6 @@ def stage_of(name):
     return {"ar_bounds_kernel": "bounds", "ar_stats_kernel": "stats", "ar_lattice_wave_kernel": "lattice",
             "ar_lattice_block_kernel": "lattice", "ar_coef_kernel": "coef", "mblank_grad_kernel": "grad",
             "mblank_grad_elem_kernel": "grad"}.get(base)
-
-
-def stats_group(row_bytes):
-    """launch_ar_stats (stats_grid, csrc/rnnt_side_host.h): lanes per row."""
-    return 4 if row_bytes <= 256 else 16 if row_bytes <= 2048 else 64
 
 
 def predict(case, cus):

@@ -10,7 +10,7 @@ A case: dtype, N, T (= maxT), U (= maxU), A, blank; `off` = byte offset of the l
 import numpy as np
 
 from tests import forms_common as C
-from tests.forms_common import STORES, object_of                        # noqa: F401  (this table's names)
+from tests.forms_common import STORES, object_of, stats_group           # noqa: F401  (this table's names)
 
 OBJECTS = {"f32": "rnnt_delay.hip", "f64": "rnnt_delay_f64.hip", "h16": "rnnt_delay_h16.hip"}
 STAGES = ("stats", "lattice", "coef", "emit", "grad")
@@ -26,11 +26,6 @@ def stage_of(name):
     return {"delay_stats_kernel": "stats", "ar_lattice_wave_kernel": "lattice", "ar_lattice_block_kernel": "lattice",
             "delay_coef_kernel": "coef", "delay_emit_kernel": "emit", "mblank_grad_kernel": "grad",
             "mblank_grad_elem_kernel": "grad"}.get(base)
-
-
-def stats_group(row_bytes):
-    """launch_delay_stats (stats_grid, csrc/rnnt_side_host.h): lanes per row."""
-    return 4 if row_bytes <= 256 else 16 if row_bytes <= 2048 else 64
 
 
 def emit_slices(U):

@@ -21,9 +21,12 @@ def stage_of(name):
             "hat_grad_elem_kernel": "grad"}.get(base)
 
 
+WIDE_ROW_BYTES = 4096   # kHatWideRowBytes: rows up to here stay on 16 lanes
+
+
 def stats_group(row_bytes):
-    """launch_hat_stats (stats_grid, csrc/rnnt_side_host.h, with HAT's 4096-byte threshold): lanes per row."""
-    return 4 if row_bytes <= 256 else 16 if row_bytes <= 4096 else 64
+    """launch_hat_stats: stats_grid with HAT's threshold."""
+    return C.stats_group(row_bytes, WIDE_ROW_BYTES)
 
 
 def predict(case, cus):
@@ -55,6 +58,12 @@ def _cases():
                _case(d + "_lat82", d, 3, 10, 600, 5, 1)]                   # lattice <8, 2>
         if d != "f64":
             cs.append(_case(d + "_lat11", d, 300, 6, 5, 5, 1))             # more blocks than compute units: lattice <1, 1>
+        # the blank in column 0 and in column A - 1, each time in a packet shared with the neighbouring row, at every group
+        # size: 256-byte rows one element off the boundary (17 packets: a second round at 4 lanes), rows just past 256 and
+        # just past 4096 bytes (257 packets or more: a second round at 64 lanes)
+        esz = STORES[d][3]
+        for g, A, kw in ((4, 256 // esz, dict(off=esz)), (16, 256 // esz + 1, {}), (64, WIDE_ROW_BYTES // esz + 1, {})):
+            cs += [_case("%s_g%d_b0" % (d, g), d, 3, 4, 3, A, 0, **kw), _case("%s_g%d_blast" % (d, g), d, 3, 4, 3, A, A - 1, **kw)]
     return cs
 
 

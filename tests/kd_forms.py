@@ -12,7 +12,7 @@ reads the teacher and goes element by element, the collapsed mode's does not and
 The statistics rule: 4 lanes per row up to 256 bytes, 16 up to 2048 bytes, 64 beyond; the t* cases sit on both sides of
 each threshold."""
 from tests import forms_common as C
-from tests.forms_common import STORES, object_of          # noqa: F401  (this table's names)
+from tests.forms_common import STORES, object_of, stats_group  # noqa: F401  (this table's names)
 
 OBJECTS = {"f32": "rnnt_kd.hip", "f64": "rnnt_kd_f64.hip", "h16": "rnnt_kd_h16.hip"}
 STAGES = ("stats", "cost", "grad")
@@ -23,11 +23,6 @@ def stage_of(name):
     base = name.split("<")[0].split("::")[-1]
     return {"kd_stats_kernel": "stats", "kd_cost_kernel": "cost", "kd_grad_kernel": "grad",
             "kd_grad_elem_kernel": "grad"}.get(base)
-
-
-def stats_group(row_bytes):
-    """launch_kd_stats (stats_grid, csrc/rnnt_side_host.h, at its default 2048-byte threshold): lanes per row."""
-    return 4 if row_bytes <= 256 else 16 if row_bytes <= 2048 else 64
 
 
 def predict(case, cus=256):

@@ -26,7 +26,7 @@ def stage_of(name):
 def lanes(case):
     """lp_lanes: the lanes of a row in the forward."""
     row = case["C"] * STORES[case["dtype"]][3]
-    return 4 if row <= NARROW_BYTES else 16 if row <= WIDE_BYTES else 64
+    return FC.stats_group(row, WIDE_BYTES, NARROW_BYTES)
 
 
 def vec(case):

@@ -8,7 +8,7 @@ A case: dtype, N, T, U (= maxU), A, blank, columns and durations of the big blan
 gradients from a 16-byte boundary (the element-wise gradient form); `lengths` = (T_b, L_b) when the case needs particular
 ones (otherwise gpu_support.ragged_lengths: one sample with T_b = 1 -- every big blank overshoots -- and one with L_b = 0)."""
 from tests import forms_common as C
-from tests.forms_common import STORES, object_of                        # noqa: F401  (this table's names)
+from tests.forms_common import STORES, object_of, stats_group           # noqa: F401  (this table's names)
 
 OBJECTS = {"f32": "rnnt_mblank.hip", "f64": "rnnt_mblank_f64.hip", "h16": "rnnt_mblank_h16.hip"}
 STAGES = ("stats", "lattice", "coef", "grad")
@@ -18,11 +18,6 @@ def stage_of(name):
     base = name.split("<")[0].split("::")[-1]
     return {"mblank_stats_kernel": "stats", "mblank_lattice_kernel": "lattice", "mblank_coef_kernel": "coef",
             "mblank_grad_kernel": "grad", "mblank_grad_elem_kernel": "grad"}.get(base)
-
-
-def stats_group(row_bytes):
-    """launch_mblank_stats (stats_grid, csrc/rnnt_side_host.h): lanes per row."""
-    return 4 if row_bytes <= 256 else 16 if row_bytes <= 2048 else 64
 
 
 def predict(case, cus):

@@ -10,7 +10,7 @@ A case: dtype, N, T (= maxT), U (= maxU), A, blank; `off` = byte offset of the l
 import numpy as np
 
 from tests import forms_common as C
-from tests.forms_common import STORES, object_of                        # noqa: F401  (this table's names)
+from tests.forms_common import STORES, object_of, stats_group           # noqa: F401  (this table's names)
 
 OBJECTS = {"f32": "rnnt_mono.hip", "f64": "rnnt_mono_f64.hip", "h16": "rnnt_mono_h16.hip"}
 STAGES = ("stats", "lattice", "coef", "grad")
@@ -22,11 +22,6 @@ def stage_of(name):
     base = name.split("<")[0].split("::")[-1]
     return {"mono_stats_kernel": "stats", "mono_lattice_wave_kernel": "lattice", "mono_lattice_block_kernel": "lattice",
             "mono_coef_kernel": "coef", "mblank_grad_kernel": "grad", "mblank_grad_elem_kernel": "grad"}.get(base)
-
-
-def stats_group(row_bytes):
-    """launch_mono_stats (stats_grid, csrc/rnnt_side_host.h): lanes per row."""
-    return 4 if row_bytes <= 256 else 16 if row_bytes <= 2048 else 64
 
 
 def predict(case, cus):
@@ -76,7 +71,11 @@ def _cases():
                _case("%s_a%d" % (d, hi), d, 5, 7, 5, hi, hi // 2),
                _case("%s_a%d" % (d, hi + 1), d, 5, 7, 5, hi + 1, hi),
                # off the 16-byte boundary: the element-wise gradient
-               _case(d + "_off", d, 5, 6, 5, 63, 62, off=esz)]
+               _case(d + "_off", d, 5, 6, 5, 63, 62, off=esz),
+               # a second round of the row reduction (csrc/rnnt_row_lse.h: more than 4 G packets) at 4 and at 64 lanes per row:
+               # 256-byte rows one element off the boundary, 17 packets each; rows just past 4096 bytes, 257 packets or more
+               _case("%s_a%d_off" % (d, lo), d, 5, 6, 5, lo, 1, off=esz),
+               _case("%s_a%d" % (d, 2 * hi + 1), d, 5, 5, 4, 2 * hi + 1, 2 * hi)]
     # A = 3 .. 7: packets straddle rows
     for A, d in ((3, "f32"), (4, "bf16"), (5, "f64"), (6, "f16"), (7, "f32")):
         cs.append(_case("%s_a%d" % (d, A), d, 6, 9, 6, A, (0, A - 1, A // 2)[A % 3]))

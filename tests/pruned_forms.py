@@ -12,7 +12,7 @@ boundary (the element-wise gradient form).  A ranges case: the same with entry "
 from tests import forms_common as C
 from tests import joint_forms as J
 from tests import kernel_forms as K
-from tests.forms_common import STORES, lattice_form, object_of          # noqa: F401  (this table's names)
+from tests.forms_common import STORES, lattice_form, object_of, stats_group  # noqa: F401  (this table's names)
 
 OBJECTS = {"f32": "rnnt_pruned.hip", "f64": "rnnt_pruned_f64.hip", "h16": "rnnt_pruned_h16.hip"}
 JOINT_OBJECT = {"joint_f32": "f32", "joint_bf16": "h16", "joint_f16": "h16"}
@@ -37,11 +37,6 @@ def stage_of(name):
     if base.startswith("joint_"):
         return "partition"
     return None
-
-
-def stats_group(row_bytes):
-    """launch_pruned_stats (stats_grid, csrc/rnnt_side_host.h): lanes per row."""
-    return 4 if row_bytes <= 256 else 16 if row_bytes <= 2048 else 64
 
 
 def predict(case, cus):

@@ -12,7 +12,7 @@ import numpy as np
 
 from tests import forms_common as C
 from tests import pstream_ref as R
-from tests.forms_common import STORES, object_of                        # noqa: F401  (this table's names)
+from tests.forms_common import STORES, object_of, stats_group           # noqa: F401  (this table's names)
 
 OBJECTS = {"f32": "rnnt_pstream.hip", "f64": "rnnt_pstream_f64.hip", "h16": "rnnt_pstream_h16.hip"}
 STAGES = ("prep", "stats", "lattice", "close", "coef", "grad")
@@ -28,11 +28,6 @@ def stage_of(name):
             "ar_lattice_block_kernel": "lattice", "mono_lattice_wave_kernel": "lattice", "mono_lattice_block_kernel": "lattice",
             "pstream_close_kernel": "close", "pstream_coef_kernel": "coef", "mblank_grad_kernel": "grad",
             "mblank_grad_elem_kernel": "grad"}.get(base)
-
-
-def stats_group(row_bytes):
-    """launch_pstream_stats (stats_grid, csrc/rnnt_side_host.h): lanes per row."""
-    return 4 if row_bytes <= 256 else 16 if row_bytes <= 2048 else 64
 
 
 def predict(case, cus):

@@ -8,7 +8,7 @@ A case: dtype, N, T, U (= maxU), A (token columns), durations; `off` = byte offs
 statistics kernel's packets then start inside the neighbouring row)."""
 from tests import forms_common as C
 from tests.forms_common import STORES, object_of                        # noqa: F401  (this table's names)
-from tests.tdt_forms import stats_group
+from tests.forms_common import stats_group
 
 OBJECTS = {"f32": "rnnt_tdt_align.hip", "f64": "rnnt_tdt_align_f64.hip", "h16": "rnnt_tdt_align_h16.hip"}
 STAGES = ("stats", "lattice", "traceback")

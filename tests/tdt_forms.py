@@ -7,7 +7,7 @@ exactly the predicted kernels ran.
 A case: dtype, N, T, U (= maxU), A (token columns), durations; `off` = byte offset of the logits and gradients from a 16-byte
 boundary (the element-wise gradient form)."""
 from tests import forms_common as C
-from tests.forms_common import STORES, object_of                        # noqa: F401  (this table's names)
+from tests.forms_common import STORES, object_of, stats_group           # noqa: F401  (this table's names)
 
 OBJECTS = {"f32": "rnnt_tdt.hip", "f64": "rnnt_tdt_f64.hip", "h16": "rnnt_tdt_h16.hip"}
 STAGES = ("stats", "lattice", "coef", "grad")
@@ -17,11 +17,6 @@ def stage_of(name):
     base = name.split("<")[0].split("::")[-1]
     return {"tdt_stats_kernel": "stats", "tdt_lattice_kernel": "lattice", "tdt_coef_kernel": "coef",
             "tdt_grad_kernel": "grad", "tdt_grad_elem_kernel": "grad"}.get(base)
-
-
-def stats_group(row_bytes):
-    """launch_tdt_stats (stats_grid, csrc/rnnt_side_host.h): lanes per row (row_bytes: the token columns only)."""
-    return 4 if row_bytes <= 256 else 16 if row_bytes <= 2048 else 64
 
 
 def predict(case, cus):

@@ -119,6 +119,36 @@ def test_code_objects_hold_exactly_the_table():
     I.assert_side_inventory(I.need_lib(LIB), F.expected_inventory())
 
 
+def _blank_shares_a_packet(case):
+    """Some row's blank lies in a 16-byte packet that also holds elements of the neighbouring row."""
+    esz = F.STORES[case["dtype"]][3]
+    V, A, blank = 16 // esz, case["A"], case["blank"]
+    for r in range(16):
+        skip = ((case.get("off", 0) + r * A * esz) % 16) // esz
+        pk = (skip + blank) // V
+        if (pk == 0 and skip > 0) or (pk == (skip + A - 1) // V and (skip + A) % V != 0):
+            return True
+    return False
+
+
+def test_every_row_has_a_case():
+    rows = F.predicted_rows()
+    for obj, ks in F.expected_inventory().items():
+        assert ks and all((obj, k) in rows for k in ks)
+    # hat_stats_kernel is the one user of the shared row reduction's per-element hook (csrc/rnnt_row_lse.h): for every store
+    # and group size rows off a 16-byte boundary, rows that take a second round of four packets per lane, and the blank in
+    # column 0, in column A - 1 and in a packet shared with the neighbouring row
+    for d, (_, tag, _, esz) in F.STORES.items():
+        for g in (4, 16, 64):
+            cs = [c for c in F.CASES.values() if c["dtype"] == d and F.stats_group(c["A"] * esz) == g]
+            assert ("rnnt::hat_stats_kernel<%s, %d>" % (tag, g)) in {k for _, k in rows} and cs
+            got = [F.C.row_corners(esz, c["A"], g, c.get("off", 0)) for c in cs]
+            assert any(skip for skip, _ in got) and any(rounds >= 2 for _, rounds in got), (d, g, got)
+            assert any(c["blank"] == 0 for c in cs) and any(c["blank"] == c["A"] - 1 for c in cs), (d, g)
+            assert any(c["blank"] == 0 and _blank_shares_a_packet(c) for c in cs), (d, g)
+            assert any(c["blank"] == c["A"] - 1 and _blank_shares_a_packet(c) for c in cs), (d, g)
+
+
 def test_device_code_has_no_scratch():
     """No scratch (private segment 0), no spilled VGPRs (tools/check_kernel_resources.py) in any of the three code objects."""
     if shutil.which("hipcc") is None:

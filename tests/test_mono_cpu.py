@@ -167,6 +167,13 @@ def test_every_row_has_a_case():
     for g in (4, 16, 64):
         for tag in ("F32", "F64", "BF16", "F16"):
             assert "rnnt::mono_stats_kernel<rnnt::%s, %d>" % (tag, g) in ks
+    # the corners of the shared row reduction (csrc/rnnt_row_lse.h), for every store and group size: rows off a 16-byte
+    # boundary, and rows that take a second round of four packets per lane
+    for d, (_, tag, _, esz) in F.STORES.items():
+        for g in (4, 16, 64):
+            got = [F.C.row_corners(esz, c["A"], g, c.get("off", 0)) for c in F.CASES.values()
+                   if c["dtype"] == d and F.stats_group(c["A"] * esz) == g]
+            assert any(skip for skip, _ in got) and any(rounds >= 2 for _, rounds in got), (d, g, got)
     for obj, lat in (("f32", "float"), ("f64", "double"), ("h16", "float")):
         for form in ("wave", "block"):
             assert (obj, "rnnt::mono_lattice_%s_kernel<%s>" % (form, lat)) in rows

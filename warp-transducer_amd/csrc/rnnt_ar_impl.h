@@ -41,11 +41,10 @@ static bool launch_ar_stats(const typename Tag::store* acts, const int* labels, 
     const StatsGrid sg = stats_grid(static_cast<size_t>(A) * sizeof(typename Tag::store), static_cast<long long>(maxT) * maxU);
     for (int b0 = 0; b0 < N; b0 += kGridSamples) {
         const dim3 grid(sg.gx, grid_samples(N, b0));
-#define RNNT_ARSTATS(GG)                                                                                               \
-        hipLaunchKernelGGL((ar_stats_kernel<Tag, GG>), grid, dim3(256), 0, s, acts, labels, xlen, ylen, bd.e, bd.l, bd.ok, \
-                           tab, maxT, maxU, A, blank, b0, poison)
-        if (sg.G == 4) RNNT_ARSTATS(4); else if (sg.G == 16) RNNT_ARSTATS(16); else RNNT_ARSTATS(64);
-#undef RNNT_ARSTATS
+        stats_dispatch(sg.G, [&](auto g) {
+            hipLaunchKernelGGL((ar_stats_kernel<Tag, decltype(g)::value>), grid, dim3(256), 0, s, acts,
+                               labels, xlen, ylen, bd.e, bd.l, bd.ok, tab, maxT, maxU, A, blank, b0, poison);
+        });
     }
     return hipGetLastError() == hipSuccess;
 }

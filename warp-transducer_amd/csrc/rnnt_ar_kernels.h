@@ -93,8 +93,8 @@ __device__ __forceinline__ bool ar_live(int t, int eu, int lu) { return eu <= t 
 
 // ------------------------------------------------------------------------------------------
 // Stage 1.  G lanes per row (G = 4, 16, 64), 256 / G rows per block.  grid = (ceil(maxT * maxU * G / 256), N slice): the
-// launch covers every row and the groups of rows outside the band leave after reading the sample's two bounds.  The row
-// reduction of mono_stats_kernel, for band rows only.
+// launch covers every row and the groups of rows outside the band leave after reading the sample's two bounds; band rows
+// go through row_lse (rnnt_row_lse.h).
 template <typename Tag, int G>
 __global__ __launch_bounds__(256) void ar_stats_kernel(
         const typename Tag::store* __restrict__ acts, const int* __restrict__ labels, const int* __restrict__ xlen,
@@ -102,7 +102,6 @@ __global__ __launch_bounds__(256) void ar_stats_kernel(
         typename Tag::comp* __restrict__ tab, int maxT, int maxU, int A, int blank, int b0, int* __restrict__ poison) {
     using St = typename Tag::store;
     using C = typename Tag::comp;
-    constexpr int V = Vec<Tag>::N;
     const int b = b0 + blockIdx.y;
     const int gl = threadIdx.x & (G - 1);
     const int q = blockIdx.x * (256 / G) + static_cast<int>(threadIdx.x) / G;     // row inside the sample
@@ -119,47 +118,11 @@ __global__ __launch_bounds__(256) void ar_stats_kernel(
         return;
     }
     const bool has_lab = u < Lb && e[bu + 1] <= t;                                // (inside the band: lo_u <= t <= hi_u)
-    int lab = blank;
-    if (u < Lb) {
-        lab = labels[static_cast<size_t>(b) * (maxU - 1) + u];
-        lab = lab < 0 ? 0 : (lab >= A ? A - 1 : lab);
-    }
+    const int lab = u < Lb ? row_label(labels, b, u, maxU, A) : blank;
     const St* row = acts + tdt_cell(b, t, u, maxT, maxU) * A;
     const C xb = load1<Tag>(row + blank);
     const C xl = load1<Tag>(row + lab);
-
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(row);
-    const int skip = static_cast<int>((addr & 15u) / sizeof(St));
-    const u32x4* vp = reinterpret_cast<const u32x4*>(addr & ~static_cast<uintptr_t>(15));
-    const int npk = (skip + A + V - 1) / V;
-    C m = neg_inf<C>(), s = 0;
-    for (int base = 0; base < npk; base += 4 * G) {
-        uint4 raw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                                             // all loads of the round first
-            const int i = base + gl + j * G;
-            raw[j] = make_uint4(0, 0, 0, 0);
-            if (i < npk) raw[j] = load_packet<true>(vp + i);
-        }
-        C v[4 * V];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = base + gl + j * G;
-            unpack<Tag>(raw[j], v + j * V);
-#pragma unroll
-            for (int k = 0; k < V; ++k)
-                if (static_cast<unsigned>(i * V + k - skip) >= static_cast<unsigned>(A)) v[j * V + k] = neg_inf<C>();
-        }
-        absorb<C, 4 * V>(v, m, s);
-    }
-    C M = m;
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) M = vmax(M, __shfl_xor(M, off, kWave));
-    const C shift = (M == neg_inf<C>()) ? C(0) : M;
-    C sum = s * fast_exp(m - shift);
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, kWave);
-    const C logZ = shift + acc_log(sum);
+    const C logZ = row_lse<Tag, G>(row, A, gl).log();
     if (gl != 0) return;
     // the blank edge (t, u) -> (t + 1, u) stays inside the band iff t + 1 <= l_u; the final blank leaves (T_b - 1, L_b)
     const bool has_blank = t + 1 <= lu || (t == T - 1 && u == Lb);
@@ -350,11 +313,7 @@ __global__ __launch_bounds__(256) void ar_coef_kernel(
         r[3] = static_cast<L>(kPadded);
         return;
     }
-    int lab = -1;
-    if (u < Lb) {
-        lab = labels[static_cast<size_t>(b) * (maxU - 1) + u];
-        lab = lab < 0 ? 0 : (lab >= A ? A - 1 : lab);
-    }
+    const int lab = u < Lb ? row_label(labels, b, u, maxU, A) : -1;
     const double lp = ll[b];
     if (poison[b] != 0 || !(lp - lp == 0.0)) {                       // NaN gradients on every in-lattice row
         const L nan = static_cast<L>(__builtin_nan(""));

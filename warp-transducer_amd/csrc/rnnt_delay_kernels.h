@@ -25,8 +25,8 @@ constexpr int kDelayEmitSlices = 8;     // frame slices of the narrow form of st
 constexpr int kDelayEmitNarrow = 64;    // the release rule of stage 4: up to 64 label columns -> the sliced form
 
 // ------------------------------------------------------------------------------------------
-// Stage 1.  G lanes per row (G = 4, 16, 64), 256 / G rows per block.  grid = (ceil(maxT * maxU * G / 256), N slice).  The
-// row reduction of ar_stats_kernel over every in-lattice row.  After it a cell holds [lp_blank, lp_label, logZ, -] (lp: base
+// Stage 1.  G lanes per row (G = 4, 16, 64), 256 / G rows per block.  grid = (ceil(maxT * maxU * G / 256), N slice).
+// row_lse (rnnt_row_lse.h) over every in-lattice row.  After it a cell holds [lp_blank, lp_label, logZ, -] (lp: base
 // 2; logZ: natural log; -inf = no edge); the lp carry the row's biases.
 //
 // THE GAUGE.  With p = delay_penalty and c = (T_b - 1) / 2 the header puts p (c - t) on the label edge of row (t, u).  Taken
@@ -45,7 +45,6 @@ __global__ __launch_bounds__(256) void delay_stats_kernel(
         int b0, int* __restrict__ poison) {
     using St = typename Tag::store;
     using C = typename Tag::comp;
-    constexpr int V = Vec<Tag>::N;
     const int b = b0 + blockIdx.y;
     const int gl = threadIdx.x & (G - 1);
     const int q = blockIdx.x * (256 / G) + static_cast<int>(threadIdx.x) / G;     // row inside the sample
@@ -56,47 +55,11 @@ __global__ __launch_bounds__(256) void delay_stats_kernel(
     if (t >= T || u > Lb) return;                                                 // padding: never read, never written
     C* rec = tab + tdt_cell(b, t, u, maxT, maxU) * kArRec;
     const bool has_lab = u < Lb;
-    int lab = blank;
-    if (has_lab) {
-        lab = labels[static_cast<size_t>(b) * (maxU - 1) + u];
-        lab = lab < 0 ? 0 : (lab >= A ? A - 1 : lab);
-    }
+    const int lab = has_lab ? row_label(labels, b, u, maxU, A) : blank;
     const St* row = acts + tdt_cell(b, t, u, maxT, maxU) * A;
     const C xb = load1<Tag>(row + blank);
     const C xl = load1<Tag>(row + lab);
-
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(row);
-    const int skip = static_cast<int>((addr & 15u) / sizeof(St));
-    const u32x4* vp = reinterpret_cast<const u32x4*>(addr & ~static_cast<uintptr_t>(15));
-    const int npk = (skip + A + V - 1) / V;
-    C m = neg_inf<C>(), s = 0;
-    for (int base = 0; base < npk; base += 4 * G) {
-        uint4 raw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                                             // all loads of the round first
-            const int i = base + gl + j * G;
-            raw[j] = make_uint4(0, 0, 0, 0);
-            if (i < npk) raw[j] = load_packet<true>(vp + i);
-        }
-        C v[4 * V];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = base + gl + j * G;
-            unpack<Tag>(raw[j], v + j * V);
-#pragma unroll
-            for (int k = 0; k < V; ++k)
-                if (static_cast<unsigned>(i * V + k - skip) >= static_cast<unsigned>(A)) v[j * V + k] = neg_inf<C>();
-        }
-        absorb<C, 4 * V>(v, m, s);
-    }
-    C M = m;
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) M = vmax(M, __shfl_xor(M, off, kWave));
-    const C shift = (M == neg_inf<C>()) ? C(0) : M;
-    C sum = s * fast_exp(m - shift);
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, kWave);
-    const C logZ = shift + acc_log(sum);
+    const C logZ = row_lse<Tag, G>(row, A, gl).log();
     if (gl != 0) return;
     // the row's two biases in the gauge of the note above, base 2: fp64 from the float's value, one rounding to the lattice
     // type.  The final blank (T_b - 1, L_b) -> terminal node carries none: phi is 0 at both its ends
@@ -134,11 +97,7 @@ __global__ __launch_bounds__(256) void delay_coef_kernel(
         r[3] = static_cast<L>(kPadded);
         return;
     }
-    int lab = -1;
-    if (u < Lb) {
-        lab = labels[static_cast<size_t>(b) * (maxU - 1) + u];
-        lab = lab < 0 ? 0 : (lab >= A ? A - 1 : lab);
-    }
+    const int lab = u < Lb ? row_label(labels, b, u, maxU, A) : -1;
     const double lp = ll[b];
     if (poison[b] != 0 || !(lp - lp == 0.0)) {                       // NaN gradients on every in-lattice row
         const L nan = static_cast<L>(__builtin_nan(""));

@@ -28,11 +28,11 @@ static void launch_hat_stats(Plan<typename Tag::comp>& p, const typename Tag::st
     const StatsGrid sg = stats_grid(static_cast<size_t>(p.A) * sizeof(typename Tag::store), p.cells_per_sample, kHatWideRowBytes);
     for (int b0 = 0; b0 < p.N; b0 += kGridSamples) {
         const dim3 grid(sg.gx, grid_samples(p.N, b0));
-#define RNNT_HSTATS(GG)                                                                                                \
-        hipLaunchKernelGGL((hat_stats_kernel<Tag, GG>), grid, dim3(256), 0, p.stream, acts, p.labels, p.input_lengths, \
-                           p.label_lengths, p.lp2, p.logz, p.maxT, p.maxU, p.Up, p.A, p.blank, b0, p.poison)
-        if (sg.G == 4) RNNT_HSTATS(4); else if (sg.G == 16) RNNT_HSTATS(16); else RNNT_HSTATS(64);
-#undef RNNT_HSTATS
+        stats_dispatch(sg.G, [&](auto g) {
+            hipLaunchKernelGGL((hat_stats_kernel<Tag, decltype(g)::value>), grid, dim3(256), 0, p.stream,
+                               acts, p.labels, p.input_lengths, p.label_lengths, p.lp2, p.logz, p.maxT, p.maxU, p.Up, p.A,
+                               p.blank, b0, p.poison);
+        });
     }
     p.check();
 }

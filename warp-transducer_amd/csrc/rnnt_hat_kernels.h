@@ -17,7 +17,7 @@
 //     hat_grad_elem_kernel   the same element by element, for tensors off 16-byte boundaries
 #pragma once
 
-#include "rnnt_kernels.h"
+#include "rnnt_row_lse.h"              // row_lse, row_label; through it rnnt_kernels.h
 
 namespace rnnt {
 
@@ -36,9 +36,9 @@ template <typename C> __device__ __forceinline__ C hat_sigmoid(C z) { return C(1
 
 // ------------------------------------------------------------------------------------------
 // Stage 1.  G lanes per row (G = 4, 16, 64), 256 / G rows per block; grid = (ceil(maxT * maxU * G / 256), N slice).
-// Lane g of a row's group takes the covering packets g, g + G, ..., four in flight.  Elements of the first and last packet
-// that belong to the neighbouring rows are masked to -inf, and so is the blank column, whose value the lane keeps: the
-// group reads it from lane (blank's packet) mod G.  The label logit is one scalar load issued in front of the packets.
+// The row reduction is row_lse (rnnt_row_lse.h) with its per-element hook: the blank column is masked out of the sum and
+// its value kept by the lane that met it; the group reads it from lane (blank's packet) mod G.  The label logit is one
+// scalar load issued in front of the packets.
 // A NaN blank logit, and a label equal to blank (HAT has no probability for it), make the stored logZ NaN: the lattice
 // kernel's poison check (rnnt_kernels.h, note_non_finite) then gives the sample a NaN cost and NaN gradients.
 template <typename Tag, int G>
@@ -58,52 +58,19 @@ __global__ __launch_bounds__(256) void hat_stats_kernel(
     const int t = q / maxU, u = q - t * maxU;
     if (t >= Tb || u >= Ub) return;                                               // padding: never read
     const bool has_lab = u < Ub - 1;
-    int lab = blank;
-    if (has_lab) {
-        lab = labels[static_cast<size_t>(b) * (maxU - 1) + u];
-        lab = lab < 0 ? 0 : (lab >= A ? A - 1 : lab);
-    }
+    const int lab = has_lab ? row_label(labels, b, u, maxU, A) : blank;
     const St* row = acts + (static_cast<size_t>(b) * maxT * maxU + q) * A;
     const C xl = load1<Tag>(row + lab);
-
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(row);
-    const int skip = static_cast<int>((addr & 15u) / sizeof(St));                 // elements of the first packet before the row
-    const u32x4* vp = reinterpret_cast<const u32x4*>(addr & ~static_cast<uintptr_t>(15));
-    const int npk = (skip + A + V - 1) / V;
-    const int bpos = skip + blank;                                                // the blank's element index in the packet stream
-    C m = neg_inf<C>(), s = 0, zb = 0;
-    for (int base = 0; base < npk; base += 4 * G) {
-        uint4 raw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                                             // all loads of the round first
-            const int i = base + gl + j * G;
-            raw[j] = make_uint4(0, 0, 0, 0);
-            if (i < npk) raw[j] = load_packet<true>(vp + i);
-        }
-        C v[4 * V];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = base + gl + j * G;
-            unpack<Tag>(raw[j], v + j * V);
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                const int at = i * V + e;
-                if (at == bpos && i < npk) zb = v[j * V + e];
-                if (static_cast<unsigned>(at - skip) >= static_cast<unsigned>(A) || at == bpos) v[j * V + e] = neg_inf<C>();
-            }
-        }
-        absorb<C, 4 * V>(v, m, s);
-    }
-    C M = m;
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) M = vmax(M, __shfl_xor(M, off, kWave));
-    const C shift = (M == neg_inf<C>()) ? C(0) : M;
-    C sum = s * fast_exp(m - shift);
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, kWave);
-    zb = __shfl(zb, (bpos / V) & (G - 1), G);
+    __builtin_assume(static_cast<unsigned>(blank) < static_cast<unsigned>(A));    // (make_plan refuses any other: no range test on the hook)
+    C zb = 0;                                                                     // kept by the lane whose packet holds the blank
+    const RowLse<C> z = row_lse<Tag, G>(row, A, gl, [&](int col, C x) {
+        if (col == blank) zb = x;
+        return col == blank;
+    });
+    const int skip = static_cast<int>((reinterpret_cast<uintptr_t>(row) & 15u) / sizeof(St));
+    zb = __shfl(zb, ((skip + blank) / V) & (G - 1), G);                           // the blank's packet in the row's packet stream
     if (gl != 0) return;
-    C logZ = shift + acc_log(sum);                                                // over the labels only
+    C logZ = z.log();                                                             // over the labels only
     if (zb != zb || (has_lab && lab == blank)) logZ = zb + (neg_inf<C>() - neg_inf<C>());   // NaN: poisons the sample
     LogPair<C> rec;                                                               // lattice log-probs are kept in base 2
     rec.x = vmax(-hat_softplus(-zb) * C(kLog2e), log_zero<C>());

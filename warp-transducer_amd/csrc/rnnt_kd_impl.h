@@ -74,12 +74,11 @@ static bool launch_kd_stats(const SideCall& c, const typename Tag::store* acts, 
     const StatsGrid sg = stats_grid(static_cast<size_t>(c.A) * sizeof(typename Tag::store), TU, kKdWideRowBytes);
     for (int b0 = 0; b0 < c.N; b0 += kGridSamples) {
         const dim3 grid(sg.gx, grid_samples(c.N, b0));
-#define RNNT_KSTATS(GG)                                                                                               \
-        hipLaunchKernelGGL((kd_stats_kernel<Tag, GG, Mode>), grid, dim3(256), 0, stream, acts, teach, c.labels,       \
-                           c.input_lengths, c.label_lengths, rec, lab, kl, padflag, c.opt.maxT, c.opt.maxU, c.A,      \
-                           c.opt.blank_label, b0, it)
-        if (sg.G == 4) RNNT_KSTATS(4); else if (sg.G == 16) RNNT_KSTATS(16); else RNNT_KSTATS(64);
-#undef RNNT_KSTATS
+        stats_dispatch(sg.G, [&](auto g) {
+            hipLaunchKernelGGL((kd_stats_kernel<Tag, decltype(g)::value, Mode>), grid, dim3(256), 0, stream,
+                               acts, teach, c.labels, c.input_lengths, c.label_lengths, rec, lab, kl, padflag, c.opt.maxT,
+                               c.opt.maxU, c.A, c.opt.blank_label, b0, it);
+        });
     }
     return hipGetLastError() == hipSuccess;
 }

@@ -66,6 +66,7 @@ __device__ __forceinline__ void kd_gather(const typename Tag::store* row, int co
 // the first and last packet that belong to the neighbouring rows are masked to -inf.  Padding rows (and every row of a sample
 // whose lengths do not fit the tensor) are never read: lane 0 marks the label word and leaves a zero KL.  The first thread of
 // the launch clears the batch's "some row is padding" word.
+// (row_lse, rnnt_row_lse.h, is the single-tensor form; here two tensors interleave, scaled by `it`, two more columns masked, a third accumulator in mode 1.)
 template <typename Tag, int G, int Mode>
 __global__ __launch_bounds__(256) void kd_stats_kernel(
         const typename Tag::store* acts, const typename Tag::store* teach,      // (may be the same tensor)

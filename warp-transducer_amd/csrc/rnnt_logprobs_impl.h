@@ -45,9 +45,9 @@ template <typename Tag> rnntStatus_t run_logprobs_fwd(const LogprobsCall& c) {
     C *px = static_cast<C*>(c.px), *py = static_cast<C*>(c.py), *lse = static_cast<C*>(c.lse);
     const int G = lp_lanes(static_cast<size_t>(a.C) * sizeof(St));
     const dim3 grid(static_cast<unsigned>((rows * G + 255) / 256));
-    if (G == 4) hipLaunchKernelGGL((logprobs_lse_kernel<Tag, 4>), grid, dim3(256), 0, c.stream, z, lse, a, rows);
-    else if (G == 16) hipLaunchKernelGGL((logprobs_lse_kernel<Tag, 16>), grid, dim3(256), 0, c.stream, z, lse, a, rows);
-    else hipLaunchKernelGGL((logprobs_lse_kernel<Tag, 64>), grid, dim3(256), 0, c.stream, z, lse, a, rows);
+    stats_dispatch(G, [&](auto g) {
+        hipLaunchKernelGGL((logprobs_lse_kernel<Tag, decltype(g)::value>), grid, dim3(256), 0, c.stream, z, lse, a, rows);
+    });
     if (hipGetLastError() != hipSuccess) return RNNT_STATUS_EXECUTION_FAILED;
     const long long cells = static_cast<long long>(a.B) * a.U * (a.T + 1 - a.mod);
     hipLaunchKernelGGL((logprobs_edges_kernel<Tag>), dim3(lp_grid(cells, 256)), dim3(256), 0, c.stream, z, lse, px, py, a);

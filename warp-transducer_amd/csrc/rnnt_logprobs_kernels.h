@@ -12,7 +12,7 @@
 //                           looked up once by every lane, each element is read once and written once; VEC: 16-byte packets,
 //                           else element by element
 #pragma once
-#include "rnnt_kernels.h"              // absorb, non_finite; through it rnnt_device.h
+#include "rnnt_row_lse.h"              // row_lse; through it rnnt_kernels.h (non_finite) and rnnt_device.h
 
 namespace rnnt {
 
@@ -103,15 +103,13 @@ template <> __device__ __forceinline__ float lp_nan<float>() { return __builtin_
 template <> __device__ __forceinline__ double lp_nan<double>() { return __builtin_nan(""); }
 
 // ------------------------------------------------------------------------------------------
-// Forward, stage 1.  G lanes per row, 256 / G rows per block, grid = ceil(rows * G / 256) with rows = B T K'.  The aligned
-// 16-byte packets that COVER the row are loaded, four per lane in flight (the first and last may reach into the neighbouring
-// rows: those elements are masked to -inf).  A row that is all -inf, or holds a NaN or +inf, gets NaN.
+// Forward, stage 1.  G lanes per row, 256 / G rows per block, grid = ceil(rows * G / 256) with rows = B T K'.  The row
+// reduction is row_lse (rnnt_row_lse.h).  A row that is all -inf, or holds a NaN or +inf, gets NaN.
 template <typename Tag, int G>
 __global__ __launch_bounds__(256) void logprobs_lse_kernel(const typename Tag::store* __restrict__ logits,
                                                            typename Tag::comp* __restrict__ lse, LpArgs a, long long rows) {
     using St = typename Tag::store;
     using C = typename Tag::comp;
-    constexpr int V = Vec<Tag>::N;
     const int gl = threadIdx.x & (G - 1);
     const long long q = static_cast<long long>(blockIdx.x) * (256 / G) + static_cast<int>(threadIdx.x) / G;
     if (q >= rows) return;                                                        // (whole groups leave together)
@@ -124,38 +122,7 @@ __global__ __launch_bounds__(256) void logprobs_lse_kernel(const typename Tag::s
         return;
     }
     const St* row = logits + q * a.C;
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(row);
-    const int skip = static_cast<int>((addr & 15u) / sizeof(St));
-    const u32x4* vp = reinterpret_cast<const u32x4*>(addr & ~static_cast<uintptr_t>(15));
-    const int npk = (skip + a.C + V - 1) / V;
-    C m = neg_inf<C>(), s = 0;
-    for (int base = 0; base < npk; base += 4 * G) {
-        uint4 raw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                                             // all loads of the round first
-            const int i = base + gl + j * G;
-            raw[j] = make_uint4(0, 0, 0, 0);
-            if (i < npk) raw[j] = load_packet<true>(vp + i);
-        }
-        C v[4 * V];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = base + gl + j * G;
-            unpack<Tag>(raw[j], v + j * V);
-#pragma unroll
-            for (int e = 0; e < V; ++e)
-                if (static_cast<unsigned>(i * V + e - skip) >= static_cast<unsigned>(a.C)) v[j * V + e] = neg_inf<C>();
-        }
-        absorb<C, 4 * V>(v, m, s);
-    }
-    C M = m;
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) M = vmax(M, __shfl_xor(M, off, kWave));
-    const C shift = (M == neg_inf<C>()) ? C(0) : M;
-    C sum = s * fast_exp(m - shift);
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, kWave);
-    C logZ = shift + acc_log(sum);
+    C logZ = row_lse<Tag, G>(row, a.C, gl).log();
     if (non_finite(logZ)) logZ = lp_nan<C>();
     if (gl == 0) lse[q] = logZ;
 }

@@ -56,11 +56,10 @@ static bool launch_mblank_stats(const typename Tag::store* acts, const int* labe
     const C sigma2 = static_cast<C>(static_cast<double>(sigma) * kLog2e);
     for (int b0 = 0; b0 < N; b0 += kGridSamples) {
         const dim3 grid(sg.gx, grid_samples(N, b0));
-#define RNNT_MSTATS(GG)                                                                                                \
-        hipLaunchKernelGGL((mblank_stats_kernel<Tag, GG>), grid, dim3(256), 0, s, acts, labels, xlen, ylen, tab, maxT, \
-                           maxU, A, bb, sigma2, b0, poison)
-        if (sg.G == 4) RNNT_MSTATS(4); else if (sg.G == 16) RNNT_MSTATS(16); else RNNT_MSTATS(64);
-#undef RNNT_MSTATS
+        stats_dispatch(sg.G, [&](auto g) {
+            hipLaunchKernelGGL((mblank_stats_kernel<Tag, decltype(g)::value>), grid, dim3(256), 0, s, acts,
+                               labels, xlen, ylen, tab, maxT, maxU, A, bb, sigma2, b0, poison);
+        });
     }
     return hipGetLastError() == hipSuccess;
 }

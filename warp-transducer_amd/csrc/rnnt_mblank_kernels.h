@@ -40,9 +40,7 @@ __host__ __device__ inline int mblank_rec_stride(int K) { return 4 + K; }
 
 // ------------------------------------------------------------------------------------------
 // Stage 1.  G lanes per row (G = 4, 16, 64), 256 / G rows per block.  grid = (ceil(maxT * maxU * G / 256), N slice).
-// The aligned 16-byte packets that COVER the row are loaded (the first and last may reach into the neighbouring rows: those
-// elements are masked to -inf; a packet never leaves the 16-byte granule of an element of this row), four per lane in
-// flight.  The blank, label and big-blank logits: scalar loads issued before the packets.
+// The row reduction is row_lse (rnnt_row_lse.h).  The blank, label and big-blank logits: scalar loads issued before it.
 template <typename Tag, int G>
 __global__ __launch_bounds__(256) void mblank_stats_kernel(
         const typename Tag::store* __restrict__ acts, const int* __restrict__ labels, const int* __restrict__ xlen,
@@ -50,7 +48,6 @@ __global__ __launch_bounds__(256) void mblank_stats_kernel(
         typename Tag::comp sigma2, int b0, int* __restrict__ poison) {
     using St = typename Tag::store;
     using C = typename Tag::comp;
-    constexpr int V = Vec<Tag>::N;
     const int b = b0 + blockIdx.y;
     const int gl = threadIdx.x & (G - 1);
     const int q = blockIdx.x * (256 / G) + static_cast<int>(threadIdx.x) / G;     // row inside the sample
@@ -61,50 +58,14 @@ __global__ __launch_bounds__(256) void mblank_stats_kernel(
     if (t >= T || u > Lb) return;                                                 // padding: never read
     const int K = bb.n;
     const bool has_lab = u < Lb;
-    int lab = bb.blank;
-    if (has_lab) {
-        lab = labels[static_cast<size_t>(b) * (maxU - 1) + u];
-        lab = lab < 0 ? 0 : (lab >= A ? A - 1 : lab);
-    }
+    const int lab = has_lab ? row_label(labels, b, u, maxU, A) : bb.blank;
     const St* row = acts + tdt_cell(b, t, u, maxT, maxU) * A;
     const C xb = load1<Tag>(row + bb.blank);
     const C xl = load1<Tag>(row + lab);
     C bz[kMbMaxBig];                                                              // (issued with the packets: one wait)
 #pragma unroll
     for (int j = 0; j < kMbMaxBig; ++j) bz[j] = j < K ? load1<Tag>(row + bb.col[j]) : neg_inf<C>();
-
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(row);
-    const int skip = static_cast<int>((addr & 15u) / sizeof(St));
-    const u32x4* vp = reinterpret_cast<const u32x4*>(addr & ~static_cast<uintptr_t>(15));
-    const int npk = (skip + A + V - 1) / V;
-    C m = neg_inf<C>(), s = 0;
-    for (int base = 0; base < npk; base += 4 * G) {
-        uint4 raw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                                             // all loads of the round first
-            const int i = base + gl + j * G;
-            raw[j] = make_uint4(0, 0, 0, 0);
-            if (i < npk) raw[j] = load_packet<true>(vp + i);
-        }
-        C v[4 * V];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = base + gl + j * G;
-            unpack<Tag>(raw[j], v + j * V);
-#pragma unroll
-            for (int e = 0; e < V; ++e)
-                if (static_cast<unsigned>(i * V + e - skip) >= static_cast<unsigned>(A)) v[j * V + e] = neg_inf<C>();
-        }
-        absorb<C, 4 * V>(v, m, s);
-    }
-    C M = m;
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) M = vmax(M, __shfl_xor(M, off, kWave));
-    const C shift = (M == neg_inf<C>()) ? C(0) : M;
-    C sum = s * fast_exp(m - shift);
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, kWave);
-    const C logZ = shift + acc_log(sum);
+    const C logZ = row_lse<Tag, G>(row, A, gl).log();
     if (gl != 0) return;
     C* rec = tab + tdt_cell(b, t, u, maxT, maxU) * mblank_rec_stride(K);
     rec[0] = (xb - logZ) * C(kLog2e) - sigma2;
@@ -247,11 +208,7 @@ __global__ __launch_bounds__(256) void mblank_coef_kernel(
         r[3] = static_cast<L>(kPadded);
         return;
     }
-    int lab = -1;
-    if (u < Lb) {
-        lab = labels[static_cast<size_t>(b) * (maxU - 1) + u];
-        lab = lab < 0 ? 0 : (lab >= A ? A - 1 : lab);
-    }
+    const int lab = u < Lb ? row_label(labels, b, u, maxU, A) : -1;
     const double lp = ll[b];
     if (poison[b] != 0 || !(lp - lp == 0.0)) {                       // NaN gradients on every in-lattice row
         const L nan = static_cast<L>(__builtin_nan(""));

@@ -47,7 +47,7 @@ template <typename L> __device__ __forceinline__ L mono_lse2(L x, L y) {
 
 // ------------------------------------------------------------------------------------------
 // Stage 1.  G lanes per row (G = 4, 16, 64), 256 / G rows per block.  grid = (ceil(maxT * maxU * G / 256), N slice).
-// The row reduction of mblank_stats_kernel, for band rows only.
+// row_lse (rnnt_row_lse.h) for band rows only.
 template <typename Tag, int G>
 __global__ __launch_bounds__(256) void mono_stats_kernel(
         const typename Tag::store* __restrict__ acts, const int* __restrict__ labels, const int* __restrict__ xlen,
@@ -55,7 +55,6 @@ __global__ __launch_bounds__(256) void mono_stats_kernel(
         int* __restrict__ poison) {
     using St = typename Tag::store;
     using C = typename Tag::comp;
-    constexpr int V = Vec<Tag>::N;
     const int b = b0 + blockIdx.y;
     const int gl = threadIdx.x & (G - 1);
     const int q = blockIdx.x * (256 / G) + static_cast<int>(threadIdx.x) / G;     // row inside the sample
@@ -70,47 +69,11 @@ __global__ __launch_bounds__(256) void mono_stats_kernel(
         return;
     }
     const bool has_lab = u < Lb;
-    int lab = blank;
-    if (has_lab) {
-        lab = labels[static_cast<size_t>(b) * (maxU - 1) + u];
-        lab = lab < 0 ? 0 : (lab >= A ? A - 1 : lab);
-    }
+    const int lab = has_lab ? row_label(labels, b, u, maxU, A) : blank;
     const St* row = acts + tdt_cell(b, t, u, maxT, maxU) * A;
     const C xb = load1<Tag>(row + blank);
     const C xl = load1<Tag>(row + lab);
-
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(row);
-    const int skip = static_cast<int>((addr & 15u) / sizeof(St));
-    const u32x4* vp = reinterpret_cast<const u32x4*>(addr & ~static_cast<uintptr_t>(15));
-    const int npk = (skip + A + V - 1) / V;
-    C m = neg_inf<C>(), s = 0;
-    for (int base = 0; base < npk; base += 4 * G) {
-        uint4 raw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                                             // all loads of the round first
-            const int i = base + gl + j * G;
-            raw[j] = make_uint4(0, 0, 0, 0);
-            if (i < npk) raw[j] = load_packet<true>(vp + i);
-        }
-        C v[4 * V];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = base + gl + j * G;
-            unpack<Tag>(raw[j], v + j * V);
-#pragma unroll
-            for (int e = 0; e < V; ++e)
-                if (static_cast<unsigned>(i * V + e - skip) >= static_cast<unsigned>(A)) v[j * V + e] = neg_inf<C>();
-        }
-        absorb<C, 4 * V>(v, m, s);
-    }
-    C M = m;
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) M = vmax(M, __shfl_xor(M, off, kWave));
-    const C shift = (M == neg_inf<C>()) ? C(0) : M;
-    C sum = s * fast_exp(m - shift);
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, kWave);
-    const C logZ = shift + acc_log(sum);
+    const C logZ = row_lse<Tag, G>(row, A, gl).log();
     if (gl != 0) return;
     // the blank edge (t, u) -> (t + 1, u) stays inside the band (or enters the terminal node) iff L_b - u < T_b - t
     rec[0] = Lb - u < T - t ? (xb - logZ) * C(kLog2e) : neg_inf<C>();
@@ -321,11 +284,7 @@ __global__ __launch_bounds__(256) void mono_coef_kernel(
         r[3] = static_cast<L>(kPadded);
         return;
     }
-    int lab = -1;
-    if (u < Lb) {
-        lab = labels[static_cast<size_t>(b) * (maxU - 1) + u];
-        lab = lab < 0 ? 0 : (lab >= A ? A - 1 : lab);
-    }
+    const int lab = u < Lb ? row_label(labels, b, u, maxU, A) : -1;
     const double lp = ll[b];
     if (poison[b] != 0 || !(lp - lp == 0.0)) {                       // NaN gradients on every in-lattice row
         const L nan = static_cast<L>(__builtin_nan(""));

@@ -33,11 +33,11 @@ static void launch_pruned_stats(Plan<typename Tag::comp>& p, const typename Tag:
     const StatsGrid sg = stats_grid(static_cast<size_t>(p.A) * sizeof(typename Tag::store), static_cast<long long>(p.maxT) * S);
     for (int b0 = 0; b0 < p.N; b0 += kGridSamples) {
         const dim3 grid(sg.gx, grid_samples(p.N, b0));
-#define RNNT_PSTATS(GG)                                                                                              \
-        hipLaunchKernelGGL((pruned_stats_kernel<Tag, GG>), grid, dim3(256), 0, p.stream, acts, win, p.labels,        \
-                           p.label_lengths, p.lp2, p.logz, p.maxT, p.maxU, p.Up, S, p.A, p.blank, b0, p.poison)
-        if (sg.G == 4) RNNT_PSTATS(4); else if (sg.G == 16) RNNT_PSTATS(16); else RNNT_PSTATS(64);
-#undef RNNT_PSTATS
+        stats_dispatch(sg.G, [&](auto g) {
+            hipLaunchKernelGGL((pruned_stats_kernel<Tag, decltype(g)::value>), grid, dim3(256), 0, p.stream,
+                               acts, win, p.labels, p.label_lengths, p.lp2, p.logz, p.maxT, p.maxU, p.Up, S, p.A, p.blank,
+                               b0, p.poison);
+        });
     }
     p.check();
 }

@@ -19,7 +19,7 @@
 //   pruned_ranges_kernel         per sample the clamp to reachable windows, the monotone pass and the overlap pass
 #pragma once
 
-#include "rnnt_kernels.h"
+#include "rnnt_row_lse.h"              // row_lse, row_label; through it rnnt_kernels.h
 
 namespace rnnt {
 
@@ -74,8 +74,7 @@ static __global__ __launch_bounds__(256) void pruned_prep_kernel(
 
 // ------------------------------------------------------------------------------------------
 // Stage 1.  G lanes per row (G = 4, 16, 64), 256 / G rows per block.  grid = (ceil(maxT * S * G / 256), N slice).
-// The aligned 16-byte packets that COVER the row are loaded (the first and last may reach into the neighbouring rows: those
-// elements are masked to -inf; a packet never leaves the 16-byte granule of an element of this row), four per lane in flight.
+// The row reduction is row_lse (rnnt_row_lse.h).
 template <typename Tag, int G>
 __global__ __launch_bounds__(256) void pruned_stats_kernel(
         const typename Tag::store* __restrict__ acts, const int2* __restrict__ win, const int* __restrict__ labels,
@@ -83,7 +82,6 @@ __global__ __launch_bounds__(256) void pruned_stats_kernel(
         int maxT, int maxU, int Up, int S, int A, int blank, int b0, int* __restrict__ poison) {
     using St = typename Tag::store;
     using C = typename Tag::comp;
-    constexpr int V = Vec<Tag>::N;
     const int b = b0 + blockIdx.y;
     const int gl = threadIdx.x & (G - 1);
     const int q = blockIdx.x * (256 / G) + static_cast<int>(threadIdx.x) / G;     // row inside the sample
@@ -93,47 +91,11 @@ __global__ __launch_bounds__(256) void pruned_stats_kernel(
     if (k >= w.y) return;                                                         // padding: never read
     const int u = w.x + k;
     const bool has_lab = u < ylen[b];
-    int lab = blank;
-    if (has_lab) {
-        lab = labels[static_cast<size_t>(b) * (maxU - 1) + u];
-        lab = lab < 0 ? 0 : (lab >= A ? A - 1 : lab);
-    }
+    const int lab = has_lab ? row_label(labels, b, u, maxU, A) : blank;
     const St* row = acts + (static_cast<size_t>(b) * maxT * S + q) * A;
     const C xb = load1<Tag>(row + blank);
     const C xl = load1<Tag>(row + lab);
-
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(row);
-    const int skip = static_cast<int>((addr & 15u) / sizeof(St));
-    const u32x4* vp = reinterpret_cast<const u32x4*>(addr & ~static_cast<uintptr_t>(15));
-    const int npk = (skip + A + V - 1) / V;
-    C m = neg_inf<C>(), s = 0;
-    for (int base = 0; base < npk; base += 4 * G) {
-        uint4 raw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                                             // all loads of the round first
-            const int i = base + gl + j * G;
-            raw[j] = make_uint4(0, 0, 0, 0);
-            if (i < npk) raw[j] = load_packet<true>(vp + i);
-        }
-        C v[4 * V];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = base + gl + j * G;
-            unpack<Tag>(raw[j], v + j * V);
-#pragma unroll
-            for (int e = 0; e < V; ++e)
-                if (static_cast<unsigned>(i * V + e - skip) >= static_cast<unsigned>(A)) v[j * V + e] = neg_inf<C>();
-        }
-        absorb<C, 4 * V>(v, m, s);
-    }
-    C M = m;
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) M = vmax(M, __shfl_xor(M, off, kWave));
-    const C shift = (M == neg_inf<C>()) ? C(0) : M;
-    C sum = s * fast_exp(m - shift);
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, kWave);
-    const C logZ = shift + acc_log(sum);
+    const C logZ = row_lse<Tag, G>(row, A, gl).log();
     if (gl == 0) {
         LogPair<C> rec;                                                           // base-2 log-probs, as the lattice keeps them
         rec.x = vmax((xb - logZ) * C(kLog2e), log_zero<C>());

@@ -39,11 +39,10 @@ static bool launch_pstream_stats(const typename Tag::store* acts, const int2* wi
     const StatsGrid sg = stats_grid(static_cast<size_t>(A) * sizeof(typename Tag::store), static_cast<long long>(maxT) * S);
     for (int b0 = 0; b0 < N; b0 += kGridSamples) {
         const dim3 grid(sg.gx, grid_samples(N, b0));
-#define RNNT_PSTREAMSTATS(GG)                                                                                          \
-        hipLaunchKernelGGL((pstream_stats_kernel<Tag, GG>), grid, dim3(256), 0, s, acts, win, labels, xlen, ylen, tab, \
-                           maxT, maxU, S, A, blank, mod, penalty, b0, poison)
-        if (sg.G == 4) RNNT_PSTREAMSTATS(4); else if (sg.G == 16) RNNT_PSTREAMSTATS(16); else RNNT_PSTREAMSTATS(64);
-#undef RNNT_PSTREAMSTATS
+        stats_dispatch(sg.G, [&](auto g) {
+            hipLaunchKernelGGL((pstream_stats_kernel<Tag, decltype(g)::value>), grid, dim3(256), 0, s, acts,
+                               win, labels, xlen, ylen, tab, maxT, maxU, S, A, blank, mod, penalty, b0, poison);
+        });
     }
     return hipGetLastError() == hipSuccess;
 }

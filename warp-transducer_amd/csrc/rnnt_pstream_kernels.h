@@ -104,9 +104,7 @@ __global__ __launch_bounds__(256) void pstream_prep_kernel(
 
 // ------------------------------------------------------------------------------------------
 // Stage 1.  G lanes per row (G = 4, 16, 64), 256 / G rows per block.  grid = (ceil(maxT * S * G / 256), N slice).  The row
-// reduction of pruned_stats_kernel / delay_stats_kernel: the aligned 16-byte packets that COVER the row are loaded (the
-// first and last may reach into the neighbouring rows: those elements are masked to -inf), four per lane in flight.  After
-// it cell (t, s_t + k) holds [lp_blank, lp_label, logZ, 0] (lp: base 2; logZ: natural log; -inf = no edge); the lp carry
+// reduction is row_lse (rnnt_row_lse.h).  After it cell (t, s_t + k) holds [lp_blank, lp_label, logZ, 0] (lp: base 2; logZ: natural log; -inf = no edge); the lp carry
 // the row's biases.
 //
 // THE GAUGE.  With p = delay_penalty and c = (T_b - 1) / 2 the header puts p (c - t) on the label edge of row (t, u).  Taken
@@ -131,7 +129,6 @@ __global__ __launch_bounds__(256) void pstream_stats_kernel(
         int S, int A, int blank, int mod, float penalty, int b0, int* __restrict__ poison) {
     using St = typename Tag::store;
     using C = typename Tag::comp;
-    constexpr int V = Vec<Tag>::N;
     const int b = b0 + blockIdx.y;
     const int gl = threadIdx.x & (G - 1);
     const int q = blockIdx.x * (256 / G) + static_cast<int>(threadIdx.x) / G;     // row inside the sample
@@ -143,47 +140,11 @@ __global__ __launch_bounds__(256) void pstream_stats_kernel(
     const int T = xlen[b], Lb = ylen[b];                                          // (w.y > 0: the lengths fit)
     if (!ps_row_read(mod != 0, t, u, T, Lb)) return;                              // outside the band: never read (stage 0 wrote the cell)
     const bool has_lab = u < Lb;
-    int lab = blank;
-    if (has_lab) {
-        lab = labels[static_cast<size_t>(b) * (maxU - 1) + u];
-        lab = lab < 0 ? 0 : (lab >= A ? A - 1 : lab);
-    }
+    const int lab = has_lab ? row_label(labels, b, u, maxU, A) : blank;
     const St* row = acts + (static_cast<size_t>(b) * maxT * S + q) * A;
     const C xb = load1<Tag>(row + blank);
     const C xl = load1<Tag>(row + lab);
-
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(row);
-    const int skip = static_cast<int>((addr & 15u) / sizeof(St));
-    const u32x4* vp = reinterpret_cast<const u32x4*>(addr & ~static_cast<uintptr_t>(15));
-    const int npk = (skip + A + V - 1) / V;
-    C m = neg_inf<C>(), s = 0;
-    for (int base = 0; base < npk; base += 4 * G) {
-        uint4 raw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                                             // all loads of the round first
-            const int i = base + gl + j * G;
-            raw[j] = make_uint4(0, 0, 0, 0);
-            if (i < npk) raw[j] = load_packet<true>(vp + i);
-        }
-        C v[4 * V];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = base + gl + j * G;
-            unpack<Tag>(raw[j], v + j * V);
-#pragma unroll
-            for (int e = 0; e < V; ++e)
-                if (static_cast<unsigned>(i * V + e - skip) >= static_cast<unsigned>(A)) v[j * V + e] = neg_inf<C>();
-        }
-        absorb<C, 4 * V>(v, m, s);
-    }
-    C M = m;
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) M = vmax(M, __shfl_xor(M, off, kWave));
-    const C shift = (M == neg_inf<C>()) ? C(0) : M;
-    C sum = s * fast_exp(m - shift);
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, kWave);
-    const C logZ = shift + acc_log(sum);
+    const C logZ = row_lse<Tag, G>(row, A, gl).log();
     if (gl != 0) return;
     // the row's two biases in the gauge of the note above, base 2
     const double half = 0.5 * static_cast<double>(penalty) * kLog2e;
@@ -257,11 +218,7 @@ __global__ __launch_bounds__(256) void pstream_coef_kernel(
     }
     const int u = w.x + k;
     const int T = xlen[b], Lb = ylen[b];
-    int lab = -1;
-    if (u < Lb) {
-        lab = labels[static_cast<size_t>(b) * (maxU - 1) + u];
-        lab = lab < 0 ? 0 : (lab >= A ? A - 1 : lab);
-    }
+    const int lab = u < Lb ? row_label(labels, b, u, maxU, A) : -1;
     const double lp = ll[b];
     if (poison[b] != 0 || !(lp - lp == 0.0)) {                       // NaN gradients on every in-lattice row
         const L nan = static_cast<L>(__builtin_nan(""));

@@ -6,6 +6,8 @@
 // arithmetic of the statistics and gradient launchers.  Host code only: no kernel is named here, so a library's code objects hold exactly the kernels its
 // own rnnt_X_impl.h launches.
 #pragma once
+#include <type_traits>
+
 #include "rnnt_host.h"
 
 namespace rnnt {
@@ -163,6 +165,13 @@ struct StatsGrid { int G; unsigned gx; };
 static inline StatsGrid stats_grid(size_t row_bytes, long long rows, size_t wide_bytes = 2048) {
     const int G = row_bytes <= 256 ? 4 : row_bytes <= wide_bytes ? 16 : 64;
     return {G, static_cast<unsigned>((rows * G + 255) / 256)};
+}
+// The group size as a template argument: launch(std::integral_constant<int, G>) for G = 4, 16, 64 (any other: 64).  The
+// kernel and its hipLaunchKernelGGL stay in the library's callable.
+template <typename F> static inline void stats_dispatch(int G, F&& launch) {
+    if (G == 4) launch(std::integral_constant<int, 4>{});
+    else if (G == 16) launch(std::integral_constant<int, 16>{});
+    else launch(std::integral_constant<int, 64>{});
 }
 
 // Gradient kernels: the flat packet stream needs both tensors on 16-byte boundaries; the element-wise form takes a

@@ -45,11 +45,10 @@ static bool launch_tdt_stats(const typename Tag::store* acts, const int* labels,
     const C sigma2 = static_cast<C>(static_cast<double>(sigma) * kLog2e);
     for (int b0 = 0; b0 < N; b0 += kGridSamples) {
         const dim3 grid(sg.gx, grid_samples(N, b0));
-#define RNNT_TSTATS(GG)                                                                                              \
-        hipLaunchKernelGGL((tdt_stats_kernel<Tag, GG>), grid, dim3(256), 0, s, acts, labels, xlen, ylen, tab, maxT,  \
-                           maxU, A, D, blank, sigma2, b0, poison)
-        if (sg.G == 4) RNNT_TSTATS(4); else if (sg.G == 16) RNNT_TSTATS(16); else RNNT_TSTATS(64);
-#undef RNNT_TSTATS
+        stats_dispatch(sg.G, [&](auto g) {
+            hipLaunchKernelGGL((tdt_stats_kernel<Tag, decltype(g)::value>), grid, dim3(256), 0, s, acts,
+                               labels, xlen, ylen, tab, maxT, maxU, A, D, blank, sigma2, b0, poison);
+        });
     }
     return hipGetLastError() == hipSuccess;
 }
