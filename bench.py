@@ -19,8 +19,16 @@ A "step" = one pass of the hot path over one synthetic batch already resident in
 (compute_rnnt_loss incl. the costs D2H copy and stream sync).  With N>1 the batch is sharded
 (contiguous slabs of samples, one per rank) and each step adds the single RCCL
 all-reduce of the summed loss; the line then carries `multi_gpu` (ranks the backend saw, per-rank ms, the same
-per-GPU shard timed without the collective, the whole global batch on one GPU, speed-up and efficiency).  Every line carries `check`: two
-samples of the timed batch against the fp64 oracle (outside the timed region; --no-verify skips it).
+per-GPU shard timed without the collective, the whole global batch on one GPU, speed-up and efficiency).
+
+A plain run does only what the headline needs: set up, warm up, time the steps, dump, print.  Its line has the headline keys, the
+per-step and per-stage times of those very steps (and the rooflines derived from them, `roofline.traffic` from the committed
+profiles), and `check.loss_sum`.  --full adds everything that takes work of its own: `check` = two samples of the timed batch
+against the fp64 oracle (outside the timed region; --no-verify skips it), `cpu_baseline` (--no-cpu-baseline), `roofline.traffic`
+measured for the run by two profiler passes (--no-traffic-pass), `plain_step_ms` (sub-0.5 ms steps once more without the stage
+events) and, on a default one-GPU line, `other_workloads` (--no-extra).  The --no-* options only subtract from --full.
+(N > 1 lines keep `multi_gpu` whole with or without --full: the shard without the collective and the whole batch on one GPU
+are what that line's speed-up and efficiency are read against; --no-full-batch trims them.)
 --dump-outputs DIR writes what the headline's last timed step returned (costs, gradients or a fixed sample of them) as
 .npy files: the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
@@ -51,7 +59,7 @@ WORKLOADS = {
     "c5": dict(N=128, T=200, L=40, A=1024, dtype="bf16", published_ms=None),
     "c5_full": dict(N=1024, T=200, L=40, A=1024, dtype="bf16", published_ms=None),   # BASELINE config 5 whole, on ONE GPU (8.6e9 elements)
 }
-# Every default one-GPU line also carries these, each with its own oracle check (`other_workloads`; --no-extra skips them):
+# Every default one-GPU line of a --full run also carries these, each with its own oracle check (`other_workloads`; --no-extra skips them):
 # the BASELINE configurations the headline is not quoted on, config 5 whole on one GPU (the base the N > 1 lines' strong
 # scaling is read against -- the SAME key appears in those lines), and the additive joint.
 OTHER_WORKLOADS = {"c2": "c2", "c4": "c4", "c5_per_gpu": "c5", "c5_full_1024_on_one_gpu": "c5_full"}
@@ -263,8 +271,7 @@ def measure_traffic(argv_tail, kernel="grad_flat_kernel"):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             out_dir = os.path.join(tmp, ctr)
             cmd = [prof, "--pmc", ctr, "--kernel-trace", "-d", out_dir, "-o", "pmc", "--", sys.executable,
-                   os.path.abspath(__file__)] + argv_tail + ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-verify",
-                                                             "--no-traffic-pass", "--no-extra"]
+                   os.path.abspath(__file__)] + argv_tail + ["--steps", "3", "--warmup", "1"]     # (a plain run: the steps alone)
             r = subprocess.run(cmd, cwd=tmp, env=dict(os.environ, TMPDIR=tmp), capture_output=True, text=True, timeout=600)
             dbs = glob.glob(os.path.join(out_dir, "**", "*.db"), recursive=True)
             if r.returncode != 0 or not dbs:
@@ -611,11 +618,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: c3 on one GPU (the headline configuration), c5 when --gpus > 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the parity check against the fp64 oracle, the "
+                         "CPU baseline, the profiler passes behind `roofline.traffic`, `plain_step_ms` and, on a default one-GPU "
+                         "line, `other_workloads`.  Off by default: a plain run sets up, warms up, times, dumps and prints")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--cpu-samples", type=int, default=128)
-    ap.add_argument("--extra", action="store_true", help="(kept for old command lines: the other workloads are now part of every default one-GPU run)")
+    ap.add_argument("--extra", action="store_true", help="with --full: `other_workloads` also beside an explicit --workload")
     ap.add_argument("--no-extra", action="store_true",
-                    help="one GPU: skip `other_workloads` (c2, c4, c5 per GPU, config 5 whole on one GPU, additive joint)")
+                    help="with --full, one GPU: skip `other_workloads` (c2, c4, c5 per GPU, config 5 whole on one GPU, additive joint)")
     ap.add_argument("--override", default="", help="dev: override workload fields, e.g. A=4992,N=64")
     ap.add_argument("--varlen", action="store_true",
                     help="robustness run: T_b ~ U[T/2,T], L_b ~ U[L/2,L] (seed 2, maxima forced), SURVEY.md 8d")
@@ -651,19 +662,22 @@ def main():
     ap.add_argument("--no-full-batch", action="store_true",
                     help="--gpus N > 1: skip rank 0's run of the whole global batch on one GPU (multi_gpu.one_gpu_full_batch_ms)")
     ap.add_argument("--no-traffic-pass", action="store_true",
-                    help="do not run the two extra rocprofv3 --pmc passes that measure `roofline.traffic` for this run "
+                    help="with --full: do not run the two extra rocprofv3 --pmc passes that measure `roofline.traffic` for this run "
                          "(one GPU only; the figure of the newest committed profiles/r*_traffic.json is reported instead)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the headline's last timed step computed (costs, gradients: a fixed "
                          "sample when larger than %d elements) to DIR/<name>.npy, float32 / float64, rank 0" % DUMP_SAMPLE)
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the parity check of the timed batch (two samples against the fp64 oracle, outside the "
+                    help="with --full: skip the parity check of the timed batch (two samples against the fp64 oracle, outside the "
                          "timed region; its result is the JSON line's `check` object)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run: nothing but the headline's own steps (the --no-* options are what --full can be trimmed with)
+        args.no_cpu_baseline = args.no_verify = args.no_traffic_pass = args.no_extra = True
     plain_line = not (args.override or args.varlen or args.packed or args.graph or args.aux_stream or args.pinned_costs
                       or args.force_sharded or args.in_place)
     want_extra = args.gpus == 1 and not args.no_extra and (args.extra or (args.workload is None and plain_line))
@@ -944,9 +958,9 @@ def main():
             dump_outputs(dump_dir, costs, grads, out if sharded else None)
         # Small problems only: the same loop once more WITHOUT the per-stage HIP events (five event records per step
         # sit between the kernels; on a 0.08 ms step they are ~10 % of it, on c3 they are not measurable).  Reported
-        # next to `value`, which stays the contractual events-on measurement.
+        # next to `value`, which stays the contractual events-on measurement.  A run of its own: --full only.
         plain = None
-        if elapsed * 1e3 / steps < 0.5 and not sharded:
+        if args.full and elapsed * 1e3 / steps < 0.5 and not sharded:
             for _ in range(3):
                 step()
             torch.cuda.synchronize(dev)

@@ -25,7 +25,7 @@ EXPECTED_OTHER = {"c2", "c4", "c5_per_gpu", "c5_full_1024_on_one_gpu", "add_c3_f
 
 
 def test_other_workloads_are_the_baseline_configs_and_the_additive_joint():
-    """The default one-GPU line carries every BASELINE configuration and the additive joint:
+    """The default one-GPU line of a --full run carries every BASELINE configuration and the additive joint:
     the key set is part of the contract with whoever reads BENCH_rNN.json."""
     sys.path.insert(0, ROOT)
     import bench
@@ -36,12 +36,12 @@ def test_other_workloads_are_the_baseline_configs_and_the_additive_joint():
 
 @pytest.mark.gpu
 def test_default_line_carries_every_workload_with_a_passing_check():
-    """`python bench.py --gpus 1` (few steps; the CPU baseline and the PMC passes are the headline's and are covered by the
-    driver's own run): c3 stays value / roofline, `other_workloads` has the seven entries, each with ms_per_step, its
+    """`python bench.py --gpus 1 --full` (few steps; the CPU baseline and the PMC passes are the headline's and are covered by the
+    driver's own --full run): c3 stays value / roofline, `other_workloads` has the ten entries, each with ms_per_step, its
     stage times, a roofline fraction and a check against the oracle that PASSED."""
     import json
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-                          "--no-cpu-baseline", "--no-traffic-pass"], capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--no-traffic-pass"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -59,6 +59,44 @@ def test_default_line_carries_every_workload_with_a_passing_check():
         assert ("roofline" in e) or ("mfma_roofline" in e) or key.startswith("rnntloss_"), key
     assert rec["other_workloads_all_checks_passed"]
     assert other["c5_full_1024_on_one_gpu"]["ms_per_step"] > 4 * other["c5_per_gpu"]["ms_per_step"]
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="CPU-only contract")
+def test_full_is_an_option_of_every_command_line():
+    """--full parses (alone and beside the options that trim it) and the run then ends where every run without a GPU ends."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
+                          "--no-cpu-baseline", "--no-traffic-pass", "--no-extra", "--no-verify"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 2 and not out.stdout.strip()
+    assert "MI355X" in out.stderr and "usage:" not in out.stderr
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_alone():
+    """`python bench.py --gpus 1 --steps N --warmup W` without --full: one line with the headline keys and the figures of the
+    timed steps themselves, nothing that takes work of its own (no oracle check, CPU baseline, profiler pass, other workload),
+    and at most 30 s of the whole process outside its N + W steps."""
+    import json
+    import math
+    import time
+    steps, warmup = 5, 2
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)],
+                         capture_output=True, text=True, timeout=900)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["metric"].startswith("ms/batch") and rec["unit"] == "ms/batch" and rec["higher_is_better"] is False
+    assert rec["dtype"] == "f32" and rec["config"]["workload"].startswith("c3") and rec["n_gpus"] == 1
+    assert rec["value"] == rec["ms_per_step"] > 0 and rec["steps"] == steps and rec["warmup"] == warmup and rec["step_ms"]["n"] == steps
+    assert rec["stage_ms"]["grad"] > 0 and rec["roofline"]["frac"] > 0.5 and rec["path_roofline"]["frac"] > 0
+    assert math.isfinite(rec["check"]["loss_sum"]) and "passed" not in rec["check"] and "samples_checked" not in rec["check"]
+    assert "other_workloads" not in rec and "cpu_baseline" not in rec and rec["plain_step_ms"] is None
+    assert "measured for this run" not in (rec["roofline"]["traffic_source"] or "")
+    outside = wall - (steps + warmup) * rec["ms_per_step"] * 1e-3
+    print("plain run: %.2f s wall clock, %.2f s outside its steps" % (wall, outside))
+    assert outside <= 30.0, outside
 
 
 def _dumped(d):

@@ -141,7 +141,7 @@ def test_bench_two_ranks_on_one_gpu():
     instead of RCCL, which refuses two ranks on one device): the self-launcher, the shard sizes of the fixed global
     batch, rank 0's whole-batch run, the per-rank gather and the rank-0-only JSON line all run with world_size 2."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--oversubscribe-gloo", "--global-batch", "64",
-                          "--steps", "4", "--warmup", "1"], capture_output=True, text=True, timeout=900)
+                          "--steps", "4", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     assert len(out.stdout.strip().splitlines()) == 1, out.stdout[:600]          # ONE line, from rank 0 only
     line = json.loads(out.stdout.strip())
@@ -169,7 +169,7 @@ def test_bench_sharded_step_on_one_rank():
     box too: same loss sum as the plain one-GPU step on the same inputs, the JSON line as the ONLY line of stdout."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29547")
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c5", "--steps", "4", "--warmup", "1",
-            "--no-cpu-baseline", "--no-traffic-pass"]
+            "--full", "--no-cpu-baseline", "--no-traffic-pass"]
     lines = []
     for extra in (["--force-sharded"], ["--force-sharded", "--overlap-collective"], [], ["--force-sharded", "--torch-collective"]):
         out = subprocess.run(base + extra, capture_output=True, text=True, timeout=900, env=env)

@@ -8,7 +8,11 @@ cd "${GRAFT_REPO_ROOT:-.}"
 mkdir -p gpurun_out
 ( timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 ) > gpurun_out/${TAG}_pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1
-python bench.py > gpurun_out/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.err
+# the default line with everything in it (oracle checks, CPU baseline, measured traffic, other_workloads) is the --full one;
+# it lands in the folder given as the second argument (default: session_out/)
+OUT=${2:-session_out}
+mkdir -p "$OUT"
+python bench.py --full > "$OUT/${TAG}_bench_default.json" 2> "$OUT/${TAG}_bench_default.err"
 timeout 1500 tools/gpu_profile.sh "$TAG" "c3 c4 c5 c2" pmc > gpurun_out/profile.log 2>&1
 # additive joint: fp32 / bf16 / fp16 storage, kernel traces of the c3 shape; RNNTLoss through autograd
 { python tools/add_network_bench.py c3 c5f32 c4 c2; python tools/add_network_bench.py --bf16 c3 c5f32; python tools/add_network_bench.py --fp16 c3 c5f32; } 2>&1 | grep -v amdgpu.ids > gpurun_out/${TAG}_add_network_bench.log

@@ -11,7 +11,7 @@ OUT=$REPO/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for wl in $WLS; do
-  python "$REPO/bench.py" --workload $wl --steps 50 --warmup 5 --no-traffic-pass $( [ "$wl" = c3 ] || echo --no-cpu-baseline ) \
+  python "$REPO/bench.py" --workload $wl --steps 50 --warmup 5 --full --no-traffic-pass $( [ "$wl" = c3 ] || echo --no-cpu-baseline ) \
       > "$OUT/${TAG}_bench_${wl}.json" 2> "$OUT/${TAG}_bench_${wl}.err"
   rm -rf /tmp/prof_$wl
   rocprofv3 --kernel-trace --stats -d /tmp/prof_$wl -o trace -- python "$REPO/bench.py" --workload $wl --steps 20 \
